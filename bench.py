@@ -20,19 +20,24 @@ convolutions (85 % of a step's GPU time; the hand-written kernels 9 %): it moves
 ranks every rank runs its own clips (videos are independent; weak scaling, no data-path collective) and ``value`` =
 N * clips * K / max-over-ranks time.
 
+A plain run sets up, warms up, times the ``--steps`` steps and prints the JSON line (headline rate, ``ms_per_step`` and the
+roofline of the timed launches); ``--dump-outputs DIR`` also writes what the last timed step computed (see dump_outputs).
+Everything else -- roofline.modes, roofline.launch_sizes, extras, cpu_baseline -- is measured only with ``--full``.  The default
+configuration's convolutions use MIOpen's stored search result (tuning/miopen, see use_tuned_convolutions) instead of searching.
+
 The JSON line also carries
   roofline     -- the dominant hand-written kernel, bk_main = the WHOLE regional memory read in one launch (soft-max read of
                   the bank, merge of the partial results, masked cells, the q_val half of the cat), timed live with HIP
                   events recorded on its own stream around every launch of the timed region.  achieved / peak / frac are
                   SURVEY.md section 8d's figure: algorithmic bytes per launch / mean duration vs 8 TB/s HBM.  What bounds
                   the kernel is latency (fp16-operand modes: matrix pipe ~20 % busy) resp. the matrix pipe under the power cap
-                  (split mode); roofline.mfma has the pipe figures, roofline.modes the same launches in
-                  the other arithmetic modes (split = fp32-class; qx; f16);
-  extras       -- single-stream (eager and HIP-graph replay) and free-running (memorize_every = 5, N = 67, fed-back masks)
+                  (split mode); roofline.mfma has the pipe figures, roofline.modes (--full) the same launches
+                  in the other arithmetic modes (split = fp32-class; qx; f16);
+  extras       -- (--full) single-stream (eager and HIP-graph replay) and free-running (memorize_every = 5, N = 67, fed-back masks)
                   fps; whole-loop frames/s for BASELINE configs[2] (5 objects), configs[4] (720p, 3 objects, T = 20) and the
                   loader's K = 11 channel count; kernel figures for the hand-written kernels, each against SURVEY.md section
                   8d's byte formulas (rank 0, N = 1 only; taken in a child process);
-  cpu_baseline -- the oracle's CPU restatement of the same path timed on this box's host cores (rank 0, N = 1 only; bounded
+  cpu_baseline -- (--full) the oracle's CPU restatement of the same path timed on this box's host cores (rank 0, N = 1 only; bounded
                   sample): BASELINE configs[0] (T = 3, N = 4) over a sweep of thread counts, value = the best one; the T = 5
                   pinned shape and the three native ops alone at the best count and at 8 threads.
 """
@@ -348,6 +353,81 @@ def loop_fps(net, tfn, dev, B, K, n_obj, H, W, T_mem, steps, seed0=100):
             'mask_channels': K, 'frame': '%dx%d' % (H, W), 'memory_frames': T_mem, 'steps': steps}
 
 
+TUNED_DIR = os.path.join(ROOT, 'tuning', 'miopen')
+
+
+def loaded_miopen_has_version(suffix):
+    """True when the MIOpen library this process loaded (through torch) is the build whose user databases carry ``suffix`` in
+    their file name, e.g. '3_5_0_20250912-42-1199-g2584e35062': major / minor / patch agree with torch.backends.cudnn.version()
+    and the whole string is the one compiled into the library (MIOpen reads a user database only under its own version)."""
+    import mmap
+    import re
+    m = re.match(r'(\d+)_(\d+)_(\d+)_(.+)$', suffix)
+    if not m or torch.backends.cudnn.version() != int(m.group(1)) * 1000000 + int(m.group(2)) * 1000 + int(m.group(3)):
+        return False
+    libs = sorted({ln.split()[-1] for ln in open('/proc/self/maps') if 'libMIOpen' in ln and '/' in ln})
+    for lib in libs:
+        with open(lib, 'rb') as f, mmap.mmap(f.fileno(), 0, access=mmap.ACCESS_READ) as mm:
+            if mm.find(suffix.encode()) >= 0:
+                return True
+    return False
+
+
+def use_tuned_convolutions(dev):
+    """MIOpen's own choice of solver and kernel parameters for the headline configuration's convolutions, written by a find run
+    (torch.backends.cudnn.benchmark = True: an exhaustive search over ~7,300 kernel configurations, ~50 s in a fresh home
+    directory) and kept in tuning/miopen/ as MIOpen's text databases.  Handed to MIOpen as its user database (a private copy:
+    MIOpen appends to it), they let immediate mode run exactly the kernels the search picks -- same step time, no search.
+    Returns the files used, or None -- no file for this GPU and CU count, or none for the MIOpen build torch loaded (the version
+    in the file name is checked: loaded_miopen_has_version), or MIOPEN_USER_DB_PATH set by the caller -- in which case the run
+    searches as before.  Regenerate: MIOPEN_USER_DB_PATH=<empty dir> python bench.py, then copy the *.udb.txt / *.ufdb.txt it
+    wrote here."""
+    import atexit
+    import glob
+    import shutil
+    import tempfile
+    if 'MIOPEN_USER_DB_PATH' in os.environ:
+        return None
+    prop = torch.cuda.get_device_properties(dev)
+    tag = '%s%x' % (prop.gcnArchName.split(':')[0], prop.multi_processor_count)     # MIOpen's file prefix, e.g. gfx950100
+    files = []
+    for f in sorted(glob.glob(os.path.join(TUNED_DIR, tag + '.HIP.*.u*db.txt'))):
+        suffix = os.path.basename(f)[len(tag + '.HIP.'):].rsplit('.', 2)[0]            # the MIOpen version in the name
+        if loaded_miopen_has_version(suffix):
+            files.append(f)
+    if not files:
+        return None
+    tmp = tempfile.mkdtemp(prefix='rmnet_miopen_db_')
+    atexit.register(shutil.rmtree, tmp, True)
+    for f in files:
+        shutil.copy(f, tmp)
+    os.environ['MIOPEN_USER_DB_PATH'] = tmp          # (read when MIOpen opens its databases, at the first convolution)
+    return [os.path.relpath(f, ROOT) for f in files]
+
+
+DUMP_LIMIT_BYTES = 64 * 1000 * 1000      # --dump-outputs: at most 64 MB of arrays per run
+
+
+def dump_outputs(out_dir, arrays, seed=0):
+    """``--dump-outputs DIR``: write ``arrays`` ({name: tensor}) as ``DIR/<name>.npy`` in float32.  While their total fits in
+    DUMP_LIMIT_BYTES every array is written whole; otherwise each one becomes ``DIR/<name>_sample.npy``: the elements of its
+    flattened (NCHW-ordered) form at a fixed, seeded set of positions, sorted, so that two builds compare element for element.
+    Returns {file name: shape}."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    host = {k: v.detach().float().contiguous().cpu().numpy() for k, v in arrays.items()}
+    total = sum(a.nbytes for a in host.values())
+    written = {}
+    for name, a in host.items():
+        if total > DUMP_LIMIT_BYTES:
+            n = max(1, int(a.size * 0.9 * DUMP_LIMIT_BYTES / total))
+            a = a.reshape(-1)[np.unique(np.random.RandomState(seed).randint(0, a.size, size=n))]
+            name += '_sample'
+        np.save(os.path.join(out_dir, name + '.npy'), a)
+        written[name + '.npy'] = list(a.shape)
+    return written
+
+
 _T_START = time.perf_counter()
 
 
@@ -378,10 +458,17 @@ def main():
     ap.add_argument('--gpus', type=int, default=1)
     ap.add_argument('--steps', type=int, default=20)
     ap.add_argument('--warmup', type=int, default=5)
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-extras', action='store_true', help='skip the single-stream / free-running / per-kernel figures')
+    ap.add_argument('--full', action='store_true',
+                    help='also measure everything beyond the headline line: the timed launches in the other arithmetic modes and at other '
+                         'launch sizes (roofline.modes / launch_sizes), the extras and the CPU baseline (minutes)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps write the soft-max probabilities of the last step as DIR/probs.npy (float32 '
+                         '[clips, K, H, W]; a fixed, seeded sample DIR/probs_sample.npy when that exceeds 64 MB); rank 0 only')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip the CPU baseline')
+    ap.add_argument('--no-extras', action='store_true', help='with --full: skip the other modes / launch sizes and the single-stream / '
+                                                                  'free-running / per-kernel figures')
     ap.add_argument('--extras-child', action='store_true',
-                    help='(internal) compute ONLY the extras block and print it: the default run takes its extras from a child process '
+                    help='(internal) compute ONLY the extras block and print it: a --full run takes its extras from a child process '
                          'started this way, so that a fault in one of the many secondary configurations cannot take the headline line with it')
     ap.add_argument('--no-miopen-find', action='store_true',
                     help='leave torch.backends.cudnn.benchmark off (MIOpen immediate mode; ~5 %% slower convs)')
@@ -436,6 +523,12 @@ def main():
     torch.cuda.set_device(dev)
     torch.set_grad_enabled(False)
     torch.backends.cudnn.benchmark = not args.no_miopen_find
+    tuned = None
+    if not args.no_miopen_find and not args.extras_child and args.channels_last and args.clips_per_gpu == DEFAULT_CLIPS:
+        # the default configuration: the search's result is stored (tuning/miopen), not redone -- MIOpen immediate mode reads it
+        tuned = use_tuned_convolutions(dev)
+        if tuned:
+            torch.backends.cudnn.benchmark = False
 
     _phase('imports done')
     net = networks.procedural_init_(RMNet(None, read_precision=args.read_precision)).to(dev).eval()
@@ -524,6 +617,9 @@ def main():
     elapsed = rd.max_over_ranks(elapsed_local)
     assert bool(torch.isfinite(out).all())
     _phase('timed region done')
+    if args.dump_outputs and rank == 0:      # (before anything else runs on the network's buffers)
+        dumped = dump_outputs(args.dump_outputs, {'probs': out})
+        _phase('outputs written to %s: %s' % (args.dump_outputs, dumped))
     multi = None
     if grouped:
         # Outside the timed region: every rank's own rate, and the path's ONE collective step -- the gather of the per-clip
@@ -569,7 +665,7 @@ def main():
     other_modes = [m for m in ('split', 'qx', 'f16') if m != args.read_precision]
     other_ms = None
     small_ms = {}
-    if not args.no_extras and not args.extras_child and world == 1:     # (secondary figures: the one-GPU line only)
+    if args.full and not args.no_extras and not args.extras_child and world == 1:     # (secondary figures: the one-GPU line only)
         other_ms = {}
         for om in other_modes:
             bank.precision = om
@@ -654,7 +750,7 @@ def main():
     AUTO_BOUND = _rmnet_mod.AUTO_LOGIT_BOUND
     logit_max = bank.logit_max()             # (one host sync, outside the timed region) the quantity 'auto' decides on
     extras = None
-    if rank == 0 and world == 1 and not args.no_extras and not args.extras_child:
+    if rank == 0 and world == 1 and args.full and not args.no_extras and not args.extras_child:
         # The extras (single stream, HIP-graph replay, free-running clip, other configurations, every kernel alone, profiler shares) run
         # in a CHILD process: they launch a dozen secondary configurations, and a GPU fault in any of them -- round 4 met one in the
         # runtime's memset node under graph replay -- would otherwise kill this process before the headline line is printed.
@@ -891,7 +987,10 @@ def main():
                        'prev_mask': 'synthetic blob mask of frame t-1 (object ~18 % of the frame, boxes ~46 % of the cells); '
                                     'extras.free_running feeds the estimated masks back instead',
                        'sharding': 'one clip per rank',
-                       'miopen_find': not args.no_miopen_find, 'channels_last': bool(args.channels_last),
+                       'miopen_find': bool(not args.no_miopen_find and not tuned), 'miopen_tuned_settings': tuned,
+                       'miopen_convolutions': ('immediate mode reading the stored result of a MIOpen find (miopen_tuned_settings)' if tuned else
+                                               'immediate mode' if args.no_miopen_find else 'MIOpen find (exhaustive search) in this run'),
+                       'channels_last': bool(args.channels_last),
                        'hip_graph': bool(args.graph), 'clips_per_gpu': B,
                        'batchnorm_folded': bool(args.fold_bn),
                        'fused_epilogues': bool(not args.fold_bn and not args.no_fuse_epilogue)},
@@ -968,7 +1067,7 @@ def main():
             line['multi_gpu'] = multi
         if extras is not None:
             line['extras'] = extras
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             line['cpu_baseline'] = cpu_baseline()
             _phase('cpu baseline done')
         print(json.dumps(line), flush=True)

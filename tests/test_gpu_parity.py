@@ -2298,3 +2298,47 @@ def test_bench_launches_its_own_ranks():
     assert len(lines) == 1
     line = json.loads(lines[0])
     assert line['n_gpus'] == 2 and line['steps'] == 2 and line['multi_gpu']['backend'] == 'gloo' and line['value'] > 0
+
+
+def test_plain_bench_line_and_dumped_outputs(tmp_path):
+    """A plain bench.py run prints only the headline line (no secondary figures: those need --full) and --dump-outputs writes the
+    last timed step's soft-max probabilities."""
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '1', '--steps', '3', '--warmup', '1', '--clips-per-gpu', '2',
+                          '--no-miopen-find', '--dump-outputs', str(tmp_path)], capture_output=True, text=True, timeout=600, cwd=root)
+    assert out.returncode == 0, out.stderr[-3000:]
+    line = json.loads([ln for ln in out.stdout.splitlines() if ln.startswith('{')][-1])
+    assert line['steps'] == 3 and line['unit'] == 'frames/s' and line['higher_is_better'] is True and line['value'] > 0
+    assert abs(line['value'] - 2 * 3 / (line['ms_per_step'] * 3 / 1e3)) < 0.02 * line['value']
+    for key in ('extras', 'cpu_baseline'):
+        assert key not in line
+    assert 'modes' not in line['roofline'] and 'launch_sizes' not in line['roofline']
+    probs = np.load(str(tmp_path / 'probs.npy'))
+    assert probs.dtype == np.float32 and probs.shape == (2, 2, 480, 854)
+    assert np.isfinite(probs).all() and np.allclose(probs.sum(axis=1), 1.0, atol=1e-5)
+
+
+def test_default_plain_bench_uses_the_stored_tuning_and_sets_up_quickly(tmp_path):
+    """The default configuration (16 clips, channels_last) in a fresh home directory: the convolutions come from the stored MIOpen
+    databases (tuning/miopen) for the MIOpen build torch loads, no search runs, and the whole run spends well under 30 s outside its
+    timed and warm-up steps (measured on MI355X: ~7 s; an in-run search took ~50 s)."""
+    import subprocess
+    import sys
+    import time
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ('MIOPEN_USER_DB_PATH', 'WORLD_SIZE', 'RANK', 'LOCAL_RANK')}
+    env['HOME'] = str(tmp_path)
+    t0 = time.perf_counter()
+    out = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '1', '--steps', '5', '--warmup', '2'],
+                         capture_output=True, text=True, timeout=600, cwd=root, env=env)
+    wall = time.perf_counter() - t0
+    assert out.returncode == 0, out.stderr[-3000:]
+    line = json.loads([ln for ln in out.stdout.splitlines() if ln.startswith('{')][-1])
+    cfg = line['config']
+    assert cfg['clips_per_gpu'] == 16 and cfg['channels_last'] and cfg['miopen_find'] is False
+    assert cfg['miopen_tuned_settings'] and all(f.startswith('tuning/miopen/') for f in cfg['miopen_tuned_settings'])
+    assert 'stored result' in cfg['miopen_convolutions']
+    outside = wall - (5 + 2) * line['ms_per_step'] / 1e3
+    assert outside < 30.0, (wall, line['ms_per_step'])

@@ -407,3 +407,68 @@ def test_auto_read_precision_start_is_sticky_per_network():
     forced = RMNet(None, read_precision='f16')
     forced._auto_peaked = True
     assert forced.resolve_read_precision([1]) == 'f16' and forced.resolve_read_precision([5]) == 'f16'
+
+
+def test_bench_dump_outputs_whole_and_sampled(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: float32 .npy files; whole while they fit in the limit, otherwise the same seeded sample of
+    positions on every run, within the limit."""
+    import sys
+    sys.path.insert(0, ROOT)
+    import bench
+    x = torch.rand(3, 2, 40, 50).to(memory_format=torch.channels_last)
+    assert bench.dump_outputs(str(tmp_path / 'a'), {'probs': x}) == {'probs.npy': [3, 2, 40, 50]}
+    got = np.load(str(tmp_path / 'a' / 'probs.npy'))
+    assert got.dtype == np.float32 and np.array_equal(got, x.numpy())
+    monkeypatch.setattr(bench, 'DUMP_LIMIT_BYTES', 4000)
+    w1 = bench.dump_outputs(str(tmp_path / 'b'), {'probs': x})
+    w2 = bench.dump_outputs(str(tmp_path / 'c'), {'probs': x.contiguous()})
+    assert list(w1) == ['probs_sample.npy'] and w1 == w2
+    s1, s2 = np.load(str(tmp_path / 'b' / 'probs_sample.npy')), np.load(str(tmp_path / 'c' / 'probs_sample.npy'))
+    assert s1.dtype == np.float32 and 0 < s1.nbytes <= 4000 and np.array_equal(s1, s2)
+    assert np.isin(s1, x.contiguous().numpy().reshape(-1)).all()
+
+
+def test_stored_miopen_tuning_is_used_only_for_its_gpu_and_miopen_build(tmp_path, monkeypatch):
+    """bench.py's stored MIOpen databases (tuning/miopen) are handed to MIOpen only for the GPU / CU count and the MIOpen build
+    in their file names; a file named for another MIOpen version is not picked up, and a caller's MIOPEN_USER_DB_PATH wins."""
+    import sys
+    import types
+    sys.path.insert(0, ROOT)
+    import bench
+    for name in ('gfx950100.HIP.3_5_0_aaa.udb.txt', 'gfx950100.HIP.3_5_0_aaa.ufdb.txt', 'gfx950100.HIP.3_5_1_bbb.udb.txt',
+                 'gfx950100.HIP.3_5_1_bbb.ufdb.txt', 'gfx942130.HIP.3_5_0_aaa.ufdb.txt'):
+        (tmp_path / name).write_text('key=solver:params\n')
+    monkeypatch.setattr(bench, 'TUNED_DIR', str(tmp_path))
+    monkeypatch.setattr(bench, 'ROOT', str(tmp_path))
+    props = {'cu': 256}
+    monkeypatch.setattr(torch.cuda, 'get_device_properties',
+                        lambda d: types.SimpleNamespace(gcnArchName='gfx950:sramecc+:xnack-', multi_processor_count=props['cu']))
+    loaded = {'v': '3_5_0_aaa'}
+    monkeypatch.setattr(bench, 'loaded_miopen_has_version', lambda suffix: suffix == loaded['v'])
+    monkeypatch.setenv('MIOPEN_USER_DB_PATH', 'set by the caller')
+    assert bench.use_tuned_convolutions(0) is None
+    monkeypatch.delenv('MIOPEN_USER_DB_PATH')
+    got = bench.use_tuned_convolutions(0)
+    assert got == ['gfx950100.HIP.3_5_0_aaa.udb.txt', 'gfx950100.HIP.3_5_0_aaa.ufdb.txt']
+    assert sorted(os.listdir(os.environ['MIOPEN_USER_DB_PATH'])) == got          # a private copy
+    monkeypatch.delenv('MIOPEN_USER_DB_PATH')
+    loaded['v'] = '3_6_0_ccc'                                                      # another MIOpen build: nothing matches
+    assert bench.use_tuned_convolutions(0) is None and 'MIOPEN_USER_DB_PATH' not in os.environ
+    loaded['v'], props['cu'] = '3_5_0_aaa', 304                                   # another CU count
+    assert bench.use_tuned_convolutions(0) is None
+
+
+def test_miopen_version_check_reads_the_loaded_library():
+    """The version test behind the stored tuning: the committed files' version is the MIOpen build torch loads here; a neighbour
+    version (other patch level, other build of the same release) is refused."""
+    import sys
+    sys.path.insert(0, ROOT)
+    import bench
+    suffixes = {os.path.basename(f).split('.HIP.')[1].rsplit('.', 2)[0] for f in os.listdir(bench.TUNED_DIR) if f.endswith('db.txt')}
+    assert len(suffixes) == 1
+    suffix = suffixes.pop()
+    major, minor, patch, tweak = suffix.split('_', 3)
+    assert bench.loaded_miopen_has_version(suffix), (suffix, torch.backends.cudnn.version())
+    assert not bench.loaded_miopen_has_version('%s_%s_%d_%s' % (major, minor, int(patch) + 1, tweak))
+    assert not bench.loaded_miopen_has_version('%s_%s_%s_%s' % (major, minor, patch, 'other-build'))
+    assert not bench.loaded_miopen_has_version('not a version')

@@ -78,8 +78,8 @@ record)
   # three arithmetics (stamped with bench.source_hash()), SQ / TCC counters of bk_main inside the loop, stress.  Evidence -> profiles/ by hand.
   run timeout 1500 python -m pytest tests -q -m gpu --durations=15
   run python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')"
-  log "python bench.py"
-  timeout 1200 python bench.py > $out/bench_line.json 2> $out/bench.err; python tools/show_line.py $out/bench_line.json | tee -a $out/log.txt
+  log "python bench.py --full"
+  timeout 1200 python bench.py --full > $out/bench_line.json 2> $out/bench.err; python tools/show_line.py $out/bench_line.json | tee -a $out/log.txt
   bash tools/profile_round.sh > $out/profile_round.txt 2>&1; cp gpurun_out/prof/timed_region.md $out/timed_region.md; cp gpurun_out/prof/bench_line.json $out/bench_line_under_rocprof.json
   for prec in f16 qx split; do PRECISION=$prec bash tools/pmc_traffic.sh > $out/pmc_traffic_$prec.txt 2>&1; done
   cp profiles/bk_main*_hbm_traffic.json $out/
@@ -91,8 +91,8 @@ record_lite)
   # the record without the PMC passes (when GPU minutes are short): suite + smoke, default bench line, rocprofv3 table, drop-in rows, stress
   run timeout 1400 python -m pytest tests -q -m gpu --durations=15
   run python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')"
-  log "python bench.py"
-  timeout 900 python bench.py > $out/bench_line.json 2> $out/bench.err; python tools/show_line.py $out/bench_line.json | tee -a $out/log.txt
+  log "python bench.py --full"
+  timeout 900 python bench.py --full > $out/bench_line.json 2> $out/bench.err; python tools/show_line.py $out/bench_line.json | tee -a $out/log.txt
   bash tools/profile_round.sh > $out/profile_round.txt 2>&1; cp gpurun_out/prof/timed_region.md $out/timed_region.md; cp gpurun_out/prof/bench_line.json $out/bench_line_under_rocprof.json
   for flags in 0 4 8; do echo "== drop-in flags $flags"; FLAGS=$flags N=200 timeout 300 python tools/dropin_trace.py 2>&1 | tail -1; done | tee $out/dropin.txt
   for mode in f16 qx split; do RMNET_BANK_PRECISION=$mode timeout 400 python tests/stress_race.py ${STRESS_N:-60} 2>&1 | tail -1; done | tee $out/stress.txt
