@@ -269,6 +269,29 @@ int rmnet_upsample2x_add_nhwc_f32(const float *x, const float *skip, long long N
 int rmnet_affine_relu_maxpool_nhwc_f32(const float *x, const float *scale, const float *shift, long long N, int C, int H, int W,
                                        float *out, void *stream);
 
+/* C1 decoder convolutions (additive export, same ABI version): 3x3 / stride 1 / pad 1 convolution with Cout = 256 on the fp16
+ * MFMA pipes with split operands (csrc/conv3x3.hip): each fp32 operand is carried as fp16 hi + lo and each product keeps
+ * Ah*Wh + Ah*Wl + Al*Wh with fp32 accumulation -- fp32-class arithmetic.  Replaces the 256-channel convolutions of the decoder
+ * (models/rmnet.py:107-140: Decoder.convFM, Decoder.ResMM, Refine.convFS / ResFS / ResMM) together with their bias / ReLU / skip.
+ *   x    [N, H, W, Cin] fp32 (channels-last), Cin % 32 == 0;
+ *   out  [N, H, W, 256] fp32 = act(conv(pre(x)) + bias[co] + res), pre = ReLU when RMNET_CONV_RELU_IN, act = ReLU when
+ *        RMNET_CONV_RELU_OUT; bias [256] and res [N, H, W, 256] may be NULL.  out must not overlap x; it may be res itself.
+ *   wpack, w_unscale: the packed weights (layout below);
+ *   range_word: device int32, may be NULL.  Activations are split after a scaling by 2^6 (exact), so |pre(x)| must be below
+ *        65504 / 64 = 1023.5; every element outside (or NaN / Inf) is saturated and ADDED to *range_word (once per element).
+ *        A non-zero word means the output is not fp32-class: the caller checks it (no host synchronisation here).
+ * Every pointer 16-byte aligned.  RMNET_E_UNSUPPORTED for Cin % 32 != 0 or N*H*W*max(Cin, 256) >= 2^31.
+ *
+ * Weight pack (built by the caller; rmnet_amd.ops.conv3x3_pack does it in torch) for w [256][Cin][3][3] fp32:
+ *   e[co]          = 15 - ceil-exponent of max |w[co]|, i.e. max |w[co]| * 2^e[co] lies in [2^14, 2^15) (e = 0 for a zero channel);
+ *   ws             = w[co][ci][ky][kx] * 2^e[co] (exact),  hi = fp16_rne(ws),  lo = fp16_rne(ws - hi);
+ *   wpack          fp16 [9][Cin / 32][2][256][32]: [tap = 3 * ky + kx][ci / 32][plane: hi, lo][co][ci % 32]  (18 * Cin * 256 * 2 bytes);
+ *   w_unscale[co]  fp32 = 2^-e[co]. */
+#define RMNET_CONV_RELU_IN 1
+#define RMNET_CONV_RELU_OUT 2
+int rmnet_conv3x3_split_f32(const float *x, const void *wpack, const float *w_unscale, const float *bias, const float *res, int flags,
+                            int N, int H, int W, int Cin, float *out, int32_t *range_word, void *stream);
+
 /* P3/P4 tail: decoder logits -> foreground probability -> soft aggregation -> un-pad (-> soft-max over
  * the K mask channels) in one pass.  dec [n_tot,2,Hp,Wp]: 2-class logits of the objects in flight;
  * clip b owns objects [obj_begin[b], obj_begin[b+1]) (device int32 [B+1]); logit / prob [B,K,H,W] with

@@ -80,6 +80,9 @@ SIGNATURES = {
         c_f32p, c_f32p, ctypes.c_longlong, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_f32p, ctypes.c_void_p]),
     'rmnet_affine_relu_maxpool_nhwc_f32': (ctypes.c_int, [
         c_f32p, c_f32p, c_f32p, ctypes.c_longlong, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_f32p, ctypes.c_void_p]),
+    'rmnet_conv3x3_split_f32': (ctypes.c_int, [
+        c_f32p, ctypes.c_void_p, c_f32p, c_f32p, c_f32p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+        c_f32p, c_i32p, ctypes.c_void_p]),
     'rmnet_flow_affine_f32': (ctypes.c_int, [
         c_f32p, c_f32p, c_f32p, ctypes.c_int, ctypes.c_int, c_f32p, ctypes.c_void_p]),
     'rmnet_flow_affine_workspace_bytes': (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int]),

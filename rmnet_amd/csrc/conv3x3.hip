@@ -1,0 +1,238 @@
+// conv3x3.hip -- 3x3 / stride 1 / pad 1 convolution, fp32 NHWC in and out, Cout = 256, on the fp16 MFMA
+// pipes with split operands: the decoder's 256-channel convolutions (Decoder.convFM, ResMM, RF3, RF2).
+//
+// Arithmetic.  Every fp32 operand is split into fp16 hi + lo (hi = fp16(v), lo = fp16(v - hi): v = hi + lo
+// to 2^-22 relative) and each product keeps three terms, Ah*Wh + Ah*Wl + Al*Wh, accumulated in fp32 by
+// v_mfma_f32_16x16x32_f16 -- the scheme of bk_main<split> (bank.hip), fp32-class accuracy at 16/3 the
+// rate of the fp32 MFMA.  Both operands are scaled by powers of two so that their lo planes stay out of
+// fp16's subnormals (exact, undone in the epilogue):
+//   weights      per output channel by 2^e, e chosen so that max |w[co]| * 2^e lies in [2^14, 2^15)
+//                (done once by the packer, see include/rmnet_hip.h);
+//   activations  by kActScale = 2^6 in the loader (the bank's window): |x| must stay below
+//                65504 / 64 = 1023.5.  A value outside (or NaN / Inf) is clamped, and counted in the
+//                caller's range word (each element once, at the centre tap): a non-zero word means
+//                "redo these convolutions in fp32".
+//
+// GEMM view: M = N*H*W pixels, N = 256 output channels, K = 9*Cin ordered (tap, input channel), so
+// one K step of 32 is one tap x 32 contiguous input channels of NHWC memory.
+//
+// Workgroup = 512 threads (8 waves) = 128 consecutive pixels x all 256 output channels; waves are
+// 2 (pixels) x 4 (channels), each owns a 64 x 64 output tile = 4 x 4 MFMA tiles (2 x 64 accumulator
+// VGPRs: hi*hi and the cross terms apart).  The per-tap halo is not staged: the 9 taps of a pixel tile re-read the same ~(128+2W)
+// pixel rows, which stay in L2 between steps.
+//
+// Per K step (32 of K) and workgroup:
+//   global reads   activations 128 px x 32 ch x 4 B  = 16 KB   (fp32; split in registers)
+//                  weights     256 co x 32 x 2 planes x 2 B = 32 KB  (pre-split, pre-packed, L2-resident)
+//   LDS            one buffer  X hi/lo [128][32] + W hi/lo [256][32] fp16 = 48 KB, two buffers = 96 KB;
+//                  one barrier per step (store the next step's tile while the MFMAs read this one)
+//   LDS reads      per wave 8 A + 8 B fragments x 1 KB = 16 KB, per CU 128 KB (~512 clk at 256 B/clk)
+//   MFMA           per wave 4 x 4 tiles x 3 terms = 48 x v_mfma_f32_16x16x32_f16 (16 clk) = 768 clk;
+//                  two waves per SIMD -> 1536 clk per step per SIMD, which is the bound.
+//   VALU split     8 elements per thread per step (~6 instructions each), negligible next to the MFMAs.
+// Ceiling at the 1/4-resolution shape (M = 414720, Cin = 256): 3240 workgroups, 72 steps each,
+// 1536 clk/step -> ~13 rounds x 110 k clk / 2.4 GHz ~ 0.6 ms (= the 2.5 PF fp16 roof / 3).
+#include "common.h"
+
+namespace rmnet {
+namespace {
+
+typedef _Float16 half8 __attribute__((ext_vector_type(8)));
+typedef _Float16 half4 __attribute__((ext_vector_type(4)));
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+
+constexpr int kCout = 256;       // output channels (fixed)
+constexpr int kMT = 128;         // pixels per workgroup
+constexpr int kKT = 32;          // K per step (one tap x 32 input channels)
+constexpr int kThreads = 512;
+constexpr float kActScale = 64.0f;                 // 2^6
+constexpr float kActUnscale = 1.0f / 64.0f;
+constexpr float kF16Max = 65504.0f;
+constexpr int kXPlane = kMT * kKT;                 // halves per activation plane
+constexpr int kWPlane = kCout * kKT;               // halves per weight plane
+constexpr int kBufHalves = 2 * kXPlane + 2 * kWPlane;
+static_assert(2 * kBufHalves * 2 <= kLdsBytesPerCU, "LDS budget");
+
+// [row][32 halves] images (64-B rows); the 16-byte chunk index is XOR-swizzled with row bits 1..2 so that
+// the fragment reads (16 rows x 4 chunks per 64 lanes) and the tile writes spread over all banks.
+__device__ inline int swz(int row, int chunk) { return row * kKT + ((chunk ^ ((row >> 1) & 3)) << 3); }
+
+struct ConvArgs {
+  const float* x;          // [M][Cin]
+  const half8* wp;         // [9 * Cin / 32][2][256][32] fp16
+  const float* w_unscale;  // [256]
+  const float* bias;       // [256] or null
+  const float* res;        // [M][256] or null
+  float* out;              // [M][256]
+  int* range;              // or null
+  int M, H, W, Cin, relu_in, relu_out;
+};
+
+__global__ __launch_bounds__(kThreads) void conv3x3_split(ConvArgs a) {
+  __shared__ __attribute__((aligned(16))) _Float16 lds[2 * kBufHalves];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int wm = wave & 1, wn = wave >> 1;
+  const int m0 = blockIdx.x * kMT;
+  const int HW = a.H * a.W, CB = a.Cin / kKT, steps = 9 * CB;
+
+  // loader items: activations 2 x float4 per thread (pixel p = tid/8 + 64i, channels 4*(tid&7) ..),
+  // weights 4 x 16 B per thread (chunk q = tid + 512i of the step's 2048)
+  const int c4 = tid & 7;
+  int ph[2], pw[2], pm[2];
+  bool pin[2];
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    const int m = m0 + (tid >> 3) + 64 * i;
+    pin[i] = m < a.M;
+    pm[i] = pin[i] ? m : 0;
+    const int r = pm[i] % HW;
+    ph[i] = r / a.W;
+    pw[i] = r % a.W;
+  }
+  f32x4 xr[2];
+  uint4 wr[4];
+  int bad = 0;
+
+  auto load = [&](int s) {
+    const int tap = s / CB, cb = s - tap * CB;
+    const int dy = tap / 3 - 1, dx = tap % 3 - 1;
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      const int h = ph[i] + dy, w = pw[i] + dx;
+      if (pin[i] && h >= 0 && h < a.H && w >= 0 && w < a.W) {
+        const size_t off = (size_t)(pm[i] + dy * a.W + dx) * a.Cin + cb * kKT + 4 * c4;
+        xr[i] = *reinterpret_cast<const f32x4*>(a.x + off);
+      } else {
+        xr[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+      }
+    }
+    const uint4* wsrc = reinterpret_cast<const uint4*>(a.wp) + (size_t)s * (2 * kWPlane / 8);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) wr[i] = wsrc[tid + kThreads * i];
+  };
+
+  auto store = [&](int s, _Float16* buf) {
+    const bool centre = s / CB == 4;
+    _Float16* xh = buf;
+    _Float16* xl = buf + kXPlane;
+    _Float16* wb = buf + 2 * kXPlane;
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      half4 hi, lo;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        float v = xr[i][e];
+        if (a.relu_in) v = v < 0.0f ? 0.0f : v;          // (keeps NaN: it is counted below)
+        const float y = v * kActScale;
+        bad += (centre && !(fabsf(y) <= kF16Max)) ? 1 : 0;
+        const float c = fminf(fmaxf(y, -kF16Max), kF16Max);   // NaN -> -65504 (saturated, counted)
+        const _Float16 h = (_Float16)c;
+        hi[e] = h;
+        lo[e] = (_Float16)(c - (float)h);
+      }
+      const int p = (tid >> 3) + 64 * i;
+      const int o = swz(p, c4 >> 1) + 4 * (c4 & 1);
+      *reinterpret_cast<half4*>(xh + o) = hi;
+      *reinterpret_cast<half4*>(xl + o) = lo;
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int q = tid + kThreads * i;
+      const int plane = q >> 10, co = (q >> 2) & (kCout - 1), ch = q & 3;
+      *reinterpret_cast<uint4*>(wb + plane * kWPlane + swz(co, ch)) = wr[i];
+    }
+  };
+
+  // two accumulator sets: hi*hi, and the two cross terms (2^-11 smaller) -- the large sum then takes one rounding per K step
+  // instead of three
+  f32x4 acc[4][4], accx[4][4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) acc[i][j] = accx[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+  load(0);
+  store(0, lds);
+  __syncthreads();
+  const int fr = lane & 15, fc = lane >> 4;
+  for (int s = 0; s < steps; ++s) {
+    _Float16* cur = lds + (s & 1) * kBufHalves;
+    if (s + 1 < steps) load(s + 1);
+    const _Float16* xh = cur;
+    const _Float16* xl = cur + kXPlane;
+    const _Float16* wh = cur + 2 * kXPlane;
+    const _Float16* wl = wh + kWPlane;
+    half8 bh[4], bl[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int o = swz(wm * 64 + i * 16 + fr, fc);
+      bh[i] = *reinterpret_cast<const half8*>(xh + o);
+      bl[i] = *reinterpret_cast<const half8*>(xl + o);
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int o = swz(wn * 64 + j * 16 + fr, fc);
+      const half8 ah = *reinterpret_cast<const half8*>(wh + o);
+      const half8 al = *reinterpret_cast<const half8*>(wl + o);
+#pragma unroll
+      for (int i = 0; i < 4; ++i) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bh[i], acc[i][j], 0, 0, 0);
+#pragma unroll
+      for (int i = 0; i < 4; ++i) accx[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bl[i], accx[i][j], 0, 0, 0);
+#pragma unroll
+      for (int i = 0; i < 4; ++i) accx[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(al, bh[i], accx[i][j], 0, 0, 0);
+    }
+    if (s + 1 < steps) store(s + 1, lds + ((s + 1) & 1) * kBufHalves);
+    __syncthreads();
+  }
+
+  // epilogue: D[co][px] -- lane holds pixel fr of each 16-pixel tile and the 4 consecutive channels 4*fc .. of each
+  // 16-channel tile, i.e. one float4 of NHWC memory per (tile pair)
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const int co = wn * 64 + j * 16 + 4 * fc;
+    const f32x4 us = *reinterpret_cast<const f32x4*>(a.w_unscale + co) * kActUnscale;
+    const f32x4 b = a.bias ? *reinterpret_cast<const f32x4*>(a.bias + co) : f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int m = m0 + wm * 64 + i * 16 + fr;
+      if (m >= a.M) continue;
+      const size_t off = (size_t)m * kCout + co;
+      f32x4 v = (acc[i][j] + accx[i][j]) * us + b;
+      if (a.res) v += *reinterpret_cast<const f32x4*>(a.res + off);
+      if (a.relu_out) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) v[e] = v[e] < 0.0f ? 0.0f : v[e];
+      }
+      *reinterpret_cast<f32x4*>(a.out + off) = v;
+    }
+  }
+  if (a.range && bad) atomicAdd(a.range, bad);
+}
+
+}  // namespace
+}  // namespace rmnet
+
+extern "C" int rmnet_conv3x3_split_f32(const float* x, const void* wpack, const float* w_unscale, const float* bias,
+                                       const float* res, int flags, int N, int H, int W, int Cin, float* out,
+                                       int32_t* range_word, void* stream) {
+  using namespace rmnet;
+  if (!x || !wpack || !w_unscale || !out || N <= 0 || H <= 0 || W <= 0 || Cin <= 0) return RMNET_E_INVALID_ARG;
+  if (flags & ~(RMNET_CONV_RELU_IN | RMNET_CONV_RELU_OUT)) return RMNET_E_INVALID_ARG;
+  if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(wpack) | reinterpret_cast<uintptr_t>(w_unscale) |
+       reinterpret_cast<uintptr_t>(bias) | reinterpret_cast<uintptr_t>(res) | reinterpret_cast<uintptr_t>(out)) & 15)
+    return RMNET_E_INVALID_ARG;
+  if (Cin % kKT) return RMNET_E_UNSUPPORTED;
+  const long long M = (long long)N * H * W;
+  if (M * (long long)(Cin > kCout ? Cin : kCout) >= (1LL << 31)) return RMNET_E_UNSUPPORTED;   // (int pixel index, size_t offsets)
+  // out must not overlap x (other workgroups read x's halo); it may BE res (each element is read, then written, by one thread)
+  const char* xb = reinterpret_cast<const char*>(x);
+  const char* ob = reinterpret_cast<const char*>(out);
+  if (ob < xb + M * Cin * sizeof(float) && xb < ob + M * kCout * sizeof(float)) return RMNET_E_INVALID_ARG;
+  ConvArgs a;
+  a.x = x; a.wp = reinterpret_cast<const half8*>(wpack); a.w_unscale = w_unscale; a.bias = bias; a.res = res; a.out = out;
+  a.range = range_word; a.M = (int)M; a.H = H; a.W = W; a.Cin = Cin;
+  a.relu_in = (flags & RMNET_CONV_RELU_IN) != 0;
+  a.relu_out = (flags & RMNET_CONV_RELU_OUT) != 0;
+  hipLaunchKernelGGL(conv3x3_split, dim3((unsigned)((M + kMT - 1) / kMT)), dim3(kThreads), 0, (hipStream_t)stream, a);
+  return check_launch();
+}

@@ -117,6 +117,12 @@ class ResBlock(nn.Module):
         bit-identical: MIOpen may choose another solver for the bias-free convolution.)"""
         from . import ops
         c1, c2 = self.conv1, self.conv2
+        if self.downsample is None and _split_conv_ok(self, x, c1) and _split_conv_ok(self, x, c2):
+            # both convolutions on the split-fp16 kernel, pre-activation ReLU / bias / ReLU / skip inside it
+            x = x.contiguous(memory_format=torch.channels_last)
+            rw = ops.conv_range_word(x.device)
+            t = ops.conv3x3_split(x, self._wp1, self._wu1, c1.bias, relu_in=True, relu_out=True, range_word=rw)
+            return ops.conv3x3_split(t, self._wp2, self._wu2, c2.bias, res=x, range_word=rw)
         t = F.conv2d(F.relu(x), c1.weight, None, c1.stride, c1.padding)
         ops.channel_affine(t, None, c1.bias, relu=True, out=t)
         r = F.conv2d(t, c2.weight, None, c2.stride, c2.padding)
@@ -194,7 +200,13 @@ class Refine(nn.Module):
         self.scale_factor = scale_factor
 
     def forward(self, f, pm):
-        s = self.ResFS(self.convFS(f))
+        if _split_conv_ok(self, f, self.convFS):
+            from . import ops
+            f = f.contiguous(memory_format=torch.channels_last)
+            s = ops.conv3x3_split(f, self._wp, self._wu, self.convFS.bias, range_word=ops.conv_range_word(f.device))
+            s = self.ResFS(s)
+        else:
+            s = self.ResFS(self.convFS(f))
         if getattr(self, '_fused', False) and not self.training and s.is_cuda and self.scale_factor == 2:
             from . import ops
             return self.ResMM(ops.upsample2x_add(pm, s, out=s))     # s + up in one pass
@@ -215,13 +227,60 @@ class Decoder(nn.Module):
         self.pred2 = nn.Conv2d(mdim, 2, 3, padding=1)
 
     def forward(self, r4, r3, r2):
-        m4 = self.ResMM(self.convFM(r4))
+        if _split_conv_ok(self, r4, self.convFM):
+            from . import ops
+            r4 = r4.contiguous(memory_format=torch.channels_last)      # (the memory read's output is NCHW)
+            m4 = self.ResMM(ops.conv3x3_split(r4, self._wp, self._wu, self.convFM.bias, range_word=ops.conv_range_word(r4.device)))
+        else:
+            m4 = self.ResMM(self.convFM(r4))
         m3 = self.RF3(r3, m4)
         m2 = self.RF2(r2, m3)
         p2 = self.pred2(F.relu(m2))
         # (channels-last runs: back to NCHW HERE, on the 2-channel quarter-resolution map -- the decoder tail kernel reads NCHW planes, and
         #  converting after the x4 upsample would move 16x the bytes; a no-op for NCHW tensors)
         return F.interpolate(p2.contiguous(), scale_factor=4, mode='bilinear', align_corners=False)
+
+
+def split_conv_backend():
+    """'split' (default): the fused decoder convolutions run on csrc/conv3x3.hip; RMNET_CONV=miopen keeps them on MIOpen
+    (A/B switch, read at every call)."""
+    import os
+    v = os.environ.get('RMNET_CONV', 'split').lower()
+    if v not in ('split', 'miopen'):
+        raise RuntimeError('RMNET_CONV must be split or miopen, got %r' % v)
+    return v
+
+
+def _split_conv_ok(m, x, conv):
+    """The split-fp16 convolution (csrc/conv3x3.hip) serves ``conv`` of module ``m`` on input ``x``: fused epilogues on, eval, a CUDA
+    fp32 4-D input in a channels-last run (the input or the network's weights channels-last), 3x3 / stride 1 / pad 1, 256 outputs,
+    Cin % 32 == 0, and the packed weights present.  Everything else keeps the MIOpen path."""
+    if not (getattr(m, '_fused', False) and getattr(m, '_conv_split', False)) or m.training:
+        return False
+    if not (x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and x.shape[1] == conv.in_channels):
+        return False
+    if not (x.is_contiguous(memory_format=torch.channels_last) and not x.is_contiguous()
+            or conv.weight.is_contiguous(memory_format=torch.channels_last) and not conv.weight.is_contiguous()):
+        return False
+    if conv.kernel_size != (3, 3) or conv.stride != (1, 1) or conv.padding != (1, 1) or conv.dilation != (1, 1) or conv.groups != 1:
+        return False
+    return conv.out_channels == 256 and conv.in_channels % 32 == 0 and split_conv_backend() == 'split'
+
+
+def set_split_conv_(module, enable):
+    """Allow (True) or forbid (False) the split-fp16 decoder convolutions in ``module``'s fused path; returns the previous
+    state of every module touched, for ``restore_split_conv_``."""
+    prev = {}
+    for m in module.modules():
+        if isinstance(m, (ResBlock, Refine, Decoder)):
+            prev[m] = getattr(m, '_conv_split', False)
+            m._conv_split = bool(enable) and getattr(m, '_wu', getattr(m, '_wu1', None)) is not None
+    return prev
+
+
+def restore_split_conv_(prev):
+    for m, v in prev.items():
+        m._conv_split = v
 
 
 class KeyValue(nn.Module):
@@ -378,6 +437,21 @@ def fuse_epilogues_(module, enable=True):
             put(m, '_b1', sh.contiguous())
             if isinstance(m, EncoderMemory):
                 put(m, '_w5', torch.cat((m.conv1.weight, m.conv1_m.weight, m.conv1_o.weight), dim=1).contiguous())
+        elif isinstance(m, (ResBlock, Refine, Decoder)):
+            # packed split-fp16 weights of the 256-channel 3x3 convolutions (csrc/conv3x3.hip); 1-D, so .to(memory_format=...) leaves them
+            from . import ops
+            convs = {ResBlock: (('1', 'conv1'), ('2', 'conv2')), Refine: (('', 'convFS'),), Decoder: (('', 'convFM'),)}[type(m)]
+            ok = True
+            for suffix, name in convs:
+                c = getattr(m, name)
+                if c.out_channels == 256 and c.in_channels % 32 == 0 and c.kernel_size == (3, 3) \
+                        and c.weight.dtype == torch.float32:
+                    wp, wu = ops.conv3x3_pack(c.weight)
+                else:
+                    wp, wu, ok = None, None, False
+                put(m, '_wp' + suffix, wp)
+                put(m, '_wu' + suffix, wu)
+            m._conv_split = ok and enable
 
     def _refresh(mod, incompatible):
         # load_state_dict() runs the post hooks of EVERY module it descends into, so a hook on each snapshot owner
@@ -388,7 +462,8 @@ def fuse_epilogues_(module, enable=True):
                 snapshot(mod)
 
     for m in module.modules():
-        if isinstance(m, (_Bottleneck, EncoderMemory, EncoderQuery)):
+        if isinstance(m, (_Bottleneck, EncoderMemory, EncoderQuery, ResBlock, Refine, Decoder)):
+            m._fused = bool(enable)
             snapshot(m)
             handle = getattr(m, '_fuse_hook', None)
             if enable and handle is None:
@@ -396,7 +471,5 @@ def fuse_epilogues_(module, enable=True):
             elif not enable and handle is not None:
                 handle.remove()
                 m._fuse_hook = None
-            m._fused = bool(enable)
-        elif isinstance(m, (ResBlock, Refine)):
             m._fused = bool(enable)
     return module

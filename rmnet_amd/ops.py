@@ -531,6 +531,95 @@ def soft_aggregate(dec, obj_begin, K, pad, want_prob=False):
     return logit, prob
 
 
+CONV_COUT = 256                   # csrc/conv3x3.hip: output channels of the split-fp16 convolution
+CONV_RELU_IN, CONV_RELU_OUT = 1, 2  # RMNET_CONV_*
+
+
+@torch.no_grad()
+def conv3x3_pack(weight):
+    """[256, Cin, 3, 3] fp32 weight -> (wpack [9 * Cin * 256 * 2] fp16 bits as int16, w_unscale fp32 [256]) in the layout of
+    include/rmnet_hip.h (rmnet_conv3x3_split_f32): per output channel a power-of-two scale 2^e puts max |w| in
+    [2^14, 2^15), the scaled weights are split into fp16 hi = rne(ws), lo = rne(ws - hi) and laid out as
+    [tap][Cin / 32][hi, lo][co][Cin % 32].  Exact up to fp16 rounding of lo (2^-22 relative)."""
+    if weight.dim() != 4 or weight.shape[0] != CONV_COUT or tuple(weight.shape[2:]) != (3, 3) or weight.shape[1] % 32:
+        raise RuntimeError('conv3x3_pack needs a [256, Cin, 3, 3] weight with Cin % 32 == 0, got %s' % (tuple(weight.shape),))
+    if weight.dtype != torch.float32:
+        raise RuntimeError('conv3x3_pack needs fp32 weights, got %s' % weight.dtype)
+    w = weight.detach().contiguous()
+    cin = w.shape[1]
+    amax = w.abs().amax(dim=(1, 2, 3))
+    _, ex = torch.frexp(amax)                              # amax in [2^(ex-1), 2^ex)
+    e = torch.where(amax > 0, 15 - ex, torch.zeros_like(ex))
+    ws = torch.ldexp(w, e.view(-1, 1, 1, 1).to(w.dtype))   # exact: power-of-two scaling
+    hi = ws.half()
+    lo = (ws - hi.float()).half()
+    planes = torch.stack([p.reshape(CONV_COUT, cin // 32, 32, 9).permute(3, 1, 0, 2) for p in (hi, lo)], dim=2)
+    unscale = torch.ldexp(torch.ones_like(amax), (-e).to(amax.dtype))
+    return planes.contiguous().view(-1).view(torch.int16), unscale.contiguous()      # (fp16 bits held as int16: .float() leaves them)
+
+
+_range_words = {}
+
+
+def conv_range_word(device):
+    """The device's int32 range word of the split-fp16 convolutions (created on first use: call it once outside graph capture).
+    One per device, shared by every network on it: ``RMNet.forward`` zeroes it at the start of a clip and reads it at the end."""
+    idx = torch.device(device).index
+    idx = torch.cuda.current_device() if idx is None else idx
+    w = _range_words.get(idx)
+    if w is None:
+        w = _range_words[idx] = torch.zeros(1, dtype=torch.int32, device=torch.device('cuda', idx))
+    return w
+
+
+def conv3x3_split(x, wpack, w_unscale, bias=None, res=None, relu_in=False, relu_out=False, out=None, range_word=None):
+    """act(conv3x3(pre(x), w) + bias + res) for a channels-last fp32 ``x`` [N, Cin, H, W] and 256 output channels, stride 1,
+    padding 1, on the split-fp16 MFMA kernel (csrc/conv3x3.hip); ``pre`` / ``act`` = ReLU when ``relu_in`` / ``relu_out``.
+    ``wpack, w_unscale`` come from ``conv3x3_pack``.  ``out`` (channels-last, may be ``res``, must not be ``x``) defaults to a
+    new tensor.  ``range_word`` (int32 [1] on the device): activations with |pre(x)| >= 1023.5, NaN or Inf are saturated
+    and counted there -- check it before trusting the result.  No fall-back: anything else is a RuntimeError."""
+    _check_act(x, 'x')
+    if x.dim() != 4 or not x.is_contiguous(memory_format=torch.channels_last):
+        raise RuntimeError('x must be a channels-last [N, Cin, H, W] tensor')
+    N, cin, H, W = x.shape
+    if cin % 32:
+        raise RuntimeError('conv3x3_split needs Cin % 32 == 0, got %d' % cin)
+    _check(wpack, 'wpack', torch.int16)
+    if wpack.numel() != 9 * cin * CONV_COUT * 2:
+        raise RuntimeError('wpack has %d elements, a Cin = %d pack has %d' % (wpack.numel(), cin, 9 * cin * CONV_COUT * 2))
+    _check(w_unscale, 'w_unscale')
+    shape = (N, CONV_COUT, H, W)
+    for t, n in ((bias, 'bias'),):
+        if t is not None:
+            _check(t, n)
+            if t.numel() != CONV_COUT:
+                raise RuntimeError('%s must have 256 elements' % n)
+    if w_unscale.numel() != CONV_COUT:
+        raise RuntimeError('w_unscale must have 256 elements')
+    if res is not None:
+        _check_act(res, 'res')
+        if tuple(res.shape) != shape or not res.is_contiguous(memory_format=torch.channels_last):
+            raise RuntimeError('res must be a channels-last [N, 256, H, W] tensor')
+    if out is None:
+        out = torch.empty(shape, dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
+    else:
+        _check_act(out, 'out')
+        if tuple(out.shape) != shape or not out.is_contiguous(memory_format=torch.channels_last):
+            raise RuntimeError('out must be a channels-last [N, 256, H, W] tensor')
+    if range_word is not None:
+        _check(range_word, 'range_word', torch.int32)
+    for t in (wpack, w_unscale, bias, res, out, range_word):
+        if t is not None and t.device != x.device:
+            raise RuntimeError('conv3x3_split: every tensor must be on %s' % x.device)
+    flags = (CONV_RELU_IN if relu_in else 0) | (CONV_RELU_OUT if relu_out else 0)
+    lib = _lib.load()
+    with torch.cuda.device(x.device):
+        rc = lib.rmnet_conv3x3_split_f32(_ptr(x), _ptr(wpack), _ptr(w_unscale), _ptr(bias), _ptr(res), flags, N, H, W, cin,
+                                         _ptr(out), _ptr(range_word), _stream(x.device))
+    _lib.check(rc, 'rmnet_conv3x3_split_f32')
+    return out
+
+
 def affine_relu_maxpool(x, scale=None, shift=None):
     """max_pool2d(relu(x * scale[c] + shift[c]), 3, stride=2, padding=1) in one pass (csrc/epilogue.hip):
     the ResNet stem's bn1 -> relu -> maxpool without the full-resolution intermediate."""

@@ -361,7 +361,13 @@ class RMNet(nn.Module):
         frame t.  Returns the logits [B,K,H,W] -- or, after ``fuse_epilogues()``, the pair
         (logits, soft-max over K of the logits).  No host synchronisation, and no frame-dependent kernel argument
         (the bank's slot / frame count travel as a device counter): with ``commit=False`` the step can be captured
-        into a HIP graph once and replayed for every frame (``forward`` does)."""
+        into a HIP graph once and replayed for every frame (``forward`` does).
+
+        After ``fuse_epilogues()`` on a channels-last network the decoder's 256-channel convolutions run on the split-fp16 kernel,
+        which saturates activations outside |x| < 1023.5 and counts them in ``ops.conv_range_word(device)``.  ``forward``
+        zeroes and checks that word once per clip and redoes the clip on MIOpen when it is non-zero; a streaming caller of
+        ``frame_step`` must do the same itself (zero it, read it at its own sync point, redo with
+        ``networks.set_split_conv_(net, False)``)."""
         self._inference_only()
         B, K = ctx.B, ctx.K
         k4, v4, boxes, rects = self._encode_memory(prev_frame, prev_mask, ctx.n_max)
@@ -416,6 +422,10 @@ class RMNet(nn.Module):
         commit = set(range(0, N, memorize_every)) | fresh
         ctx = self._ClipContext(self, B, K, H, W, n_max, dev)
         bank = self.new_bank(ctx, sum(1 for j in commit if j <= N - 2) + 1, exact=_exact, precision=_precision)
+        # the split-fp16 decoder convolutions count activations outside their window here (read with the bank's status)
+        conv_word = ops.conv_range_word(dev) if getattr(self.decoder, '_conv_split', False) and getattr(self.decoder, '_fused', False) else None
+        if conv_word is not None:
+            conv_word.zero_()
 
         # (a bank of more than one launch's frames is read in host-planned chunks: its frame count would be baked into the capture)
         use_graph = bool(graph) and isinstance(bank, ops.MemoryBank) and bank.capacity <= ops.BANK_MAX_SLOTS
@@ -452,7 +462,20 @@ class RMNet(nn.Module):
             if return_logits:
                 logits[:, t] = logit
         overflow, timeouts, logit_max = bank.status()      # (one host sync per clip)
+        conv_range = int(conv_word.item()) if conv_word is not None else 0     # (the stream is already synchronised)
         self.last_clip = {'read_precision': getattr(bank, 'precision', 'exact'), 'logit_max': logit_max, 'reread': None}
+        if conv_range:              # an activation outside the split-fp16 convolutions' window: redo the clip on MIOpen's fp32 ones
+            from .networks import restore_split_conv_, set_split_conv_
+            prev = set_split_conv_(self, False)
+            try:
+                out = self.forward(frames, masks, optical_flows, n_objects, memorize_every, device=dev, _exact=_exact, graph=graph,
+                                   return_logits=return_logits, _precision=_precision)
+            finally:
+                restore_split_conv_(prev)
+            inner = self.last_clip['reread']
+            self.last_clip['reread'] = 'miopen: %d activation(s) outside the split convolutions\' window' % conv_range + \
+                ('; ' + inner if inner else '')
+            return out
         if overflow:                # K / V / q_key outside the split-fp16 window: redo the clip exactly
             if timeouts:
                 import warnings
