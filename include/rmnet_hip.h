@@ -292,6 +292,30 @@ int rmnet_affine_relu_maxpool_nhwc_f32(const float *x, const float *scale, const
 int rmnet_conv3x3_split_f32(const float *x, const void *wpack, const float *w_unscale, const float *bias, const float *res, int flags,
                             int N, int H, int W, int Cin, float *out, int32_t *range_word, void *stream);
 
+/* C1 trunk / key-value convolutions (additive export, same ABI version): the arithmetic, range word and flags of
+ * rmnet_conv3x3_split_f32 for kernel size ksize = 1 or 3 (padding ksize / 2), stride 1 or 2 and Cout % 64 == 0 (csrc/conv_split.hip).
+ * Replaces the ResNet-50 bottleneck convolutions (BatchNorm folded into the pack, skip add and ReLU in the epilogue) and the two
+ * KeyValue heads (one launch over their concatenated weights).
+ *   x     [N, H, W, Cin] fp32 (channels-last), Cin % 32 == 0;
+ *   out   [N, Ho, Wo, Cout] fp32 = act(conv(pre(x)) + shift[co] + res), Ho = (H + 2 * pad - ksize) / stride + 1 (Wo alike);
+ *         shift [Cout] and res [N, Ho, Wo, Cout] may be NULL; out must not overlap x, it may be res itself;
+ *   out2  NULL, or two outputs: channels [0, out_split) go to out [N, Ho, Wo, out_split] and [out_split, Cout) to
+ *         out2 [N, Ho, Wo, Cout - out_split] (0 < out_split < Cout, out_split % 4 == 0, res NULL, no overlap with x or out);
+ *   range_word: as above, each input element the convolution reads counted once (by the workgroups of the first Cout tile).
+ * Every pointer 16-byte aligned.  RMNET_E_UNSUPPORTED for another ksize / stride, Cin % 32 != 0, Cout % 64 != 0, or
+ * N*H*W*Cin or N*Ho*Wo*Cout >= 2^31.
+ *
+ * Weight pack (rmnet_amd.ops.conv_split_pack) for w [Cout][Cin][ksize][ksize] fp32 and an optional per-channel factor g [Cout]
+ * (the folded BatchNorm scale; 1 when absent):
+ *   wg             = w[co] * g[co] formed in float64;
+ *   e[co]          = 15 - ceil-exponent of max |wg[co]| (e = 0 for a zero channel);
+ *   ws             = wg * 2^e[co] (exact),  hi = fp16_rne(ws),  lo = fp16_rne(ws - hi)  (hi + lo = wg * 2^e to ~2^-22 relative);
+ *   wpack          fp16 [ksize^2][Cin / 32][2][Cout][32]: [tap = ksize * ky + kx][ci / 32][plane: hi, lo][co][ci % 32];
+ *   w_unscale[co]  fp32 = 2^-e[co].  For ksize 3 and Cout 256 without g this is rmnet_conv3x3_split_f32's pack. */
+int rmnet_conv_split_f32(const float *x, const void *wpack, const float *w_unscale, const float *shift, const float *res, int flags,
+                         int N, int H, int W, int Cin, int Cout, int ksize, int stride, float *out, float *out2, int out_split,
+                         int32_t *range_word, void *stream);
+
 /* P3/P4 tail: decoder logits -> foreground probability -> soft aggregation -> un-pad (-> soft-max over
  * the K mask channels) in one pass.  dec [n_tot,2,Hp,Wp]: 2-class logits of the objects in flight;
  * clip b owns objects [obj_begin[b], obj_begin[b+1]) (device int32 [B+1]); logit / prob [B,K,H,W] with

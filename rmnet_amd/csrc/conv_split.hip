@@ -1,0 +1,287 @@
+// conv_split.hip -- general split-fp16 implicit-GEMM convolution: kernel 1x1 or 3x3, stride 1 or 2, padding ksize / 2,
+// fp32 NHWC in and out, Cin % 32 == 0, Cout % 64 == 0.  Runs the ResNet-50 trunks' bottleneck convolutions (BatchNorm
+// folded into the pack, skip add and ReLU in the epilogue) and the fused key / value heads.
+//
+// Arithmetic: that of conv3x3.hip (see there) -- both operands carried as fp16 hi + lo, three product terms
+// Ah*Wh + Ah*Wl + Al*Wh on v_mfma_f32_16x16x32_f16 in two fp32 accumulator sets, activations scaled by the exact 2^6,
+// weights by a per-output-channel power of two chosen by the packer.  Out-of-window activations (|x| >= 1023.5, NaN, Inf)
+// are saturated and counted in the caller's range word once per input element that the convolution reads: at the tap
+// (ky, kx) with ky, kx in {pad} (stride 1, or 1x1) or {pad, 2} (3x3 / stride 2: the even rows / columns are the centre
+// tap's, the odd ones the last tap's of the output to their upper left).
+//
+// GEMM view: M = N*Ho*Wo output pixels, N = Cout, K = ksize^2 * Cin ordered (tap, input channel); one K step of 32 is one
+// tap x 32 contiguous input channels.  Workgroup = 512 threads (8 waves) = MT pixels x NT output channels, blockIdx.y
+// picks the NT-channel slice of Cout.  Waves are WM (pixels) x WN (channels), each owns TI x TJ 16x16 MFMA tiles.  Tiles
+// (chosen on the host, rmnet_conv_split_f32):
+//   Big    MT 128 x NT 256 (WM 2, WN 4, 4x4 tiles/wave)  Cout % 256 == 0 on maps that give >= 512 workgroups: the
+//          decoder kernel's shape (216 VGPRs, 96 KB of LDS -- 128 KB as allocated: one workgroup per CU);
+//   Mid    MT 128 x NT 128 (WM 2, WN 4, 4x2 tiles/wave)  Cout % 128 == 0 otherwise: the 1/16 maps (M = 25,920 at the
+//          bench shape) give only 203 Big workgroups for 256 CUs.  Held to 128 VGPRs (4 waves per SIMD) and 80 KB of
+//          LDS, two Mid workgroups share a CU, so the 406 of a 256-channel 1/16 convolution run in one round;
+//   Narrow MT 128 x NT 64  (WM 4, WN 2, 2x2 tiles/wave)  Cout = 64 (layer1 at 1/4), also two workgroups per CU.
+// Every tile's register budget is checked with -Rpass-analysis=kernel-resource-usage: no spills.
+// One LDS double buffer (X hi/lo [MT][32] + W hi/lo [NT][32] fp16), one barrier per K step, as in conv3x3.hip.
+#include "common.h"
+
+namespace rmnet {
+namespace {
+
+typedef _Float16 half8 __attribute__((ext_vector_type(8)));
+typedef _Float16 half4 __attribute__((ext_vector_type(4)));
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+
+constexpr int kKT = 32;          // K per step (one tap x 32 input channels)
+constexpr int kThreads = 512;
+constexpr float kActScale = 64.0f;                 // 2^6
+constexpr float kActUnscale = 1.0f / 64.0f;
+constexpr float kF16Max = 65504.0f;
+
+// [row][32 halves] images (64-B rows), 16-byte chunk index XOR-swizzled with row bits 1..2 (conv3x3.hip's layout)
+__device__ inline int swz(int row, int chunk) { return row * kKT + ((chunk ^ ((row >> 1) & 3)) << 3); }
+
+struct SplitArgs {
+  const float* x;          // [N][H][W][Cin]
+  const uint4* wp;         // [k*k][Cin / 32][2][Cout][32] fp16
+  const float* unscale;    // [Cout]
+  const float* shift;      // [Cout] or null
+  const float* res;        // [M][Cout] or null
+  float* out;              // [M][Cout], or [M][csplit] with out2
+  float* out2;             // null, or [M][Cout - csplit]: channels csplit .. Cout-1
+  int* range;              // or null
+  int M, H, W, Ho, Wo, Cin, Cout, csplit, ksize, stride, pad, relu_in, relu_out;
+};
+
+// WPE: waves per SIMD the register allocation must allow -- 2 (one workgroup per CU) for Big, 4 (two) for Mid / Narrow
+template <int WM, int WN, int TI, int TJ, int WPE>
+__global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(WPE))) void conv_split(SplitArgs a) {
+  static_assert(WM * WN * 64 == kThreads, "8 waves");
+  constexpr int MT = WM * TI * 16, NT = WN * TJ * 16;
+  constexpr int XI = MT / 64;                      // activation float4s per thread and step
+  constexpr int WI = NT / 64;                      // weight 16-byte chunks per thread and step
+  constexpr int kXPlane = MT * kKT, kWPlane = NT * kKT;
+  constexpr int kBufHalves = 2 * kXPlane + 2 * kWPlane;
+  static_assert(2 * kBufHalves * 2 <= kLdsBytesPerCU, "LDS budget");
+  __shared__ __attribute__((aligned(16))) _Float16 lds[2 * kBufHalves];
+
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int wm = wave % WM, wn = wave / WM;
+  const int m0 = blockIdx.x * MT, n0 = blockIdx.y * NT;
+  const int CB = a.Cin / kKT, steps = a.ksize * a.ksize * CB;
+  const int HWo = a.Ho * a.Wo;
+
+  // loader items: activations XI x float4 (pixel p = tid/8 + 64i, channels 4*(tid&7) ..), weights WI x 16 B
+  const int c4 = tid & 7;
+  int pbase[XI], ph[XI], pw[XI];      // input pixel of tap (0, 0): flat index, row, column (outside the map: not read)
+#pragma unroll
+  for (int i = 0; i < XI; ++i) {
+    const int m = m0 + (tid >> 3) + 64 * i;
+    const int n = m / HWo, r = m - n * HWo;
+    const int ho = r / a.Wo, wo = r - ho * a.Wo;
+    ph[i] = m < a.M ? ho * a.stride - a.pad : -4;       // (past M: every tap's row is < 0)
+    pw[i] = wo * a.stride - a.pad;
+    pbase[i] = (n * a.H + ph[i]) * a.W + pw[i];
+  }
+  f32x4 xr[XI];
+  uint4 wr[WI];
+  int bad = 0;
+
+  auto load = [&](int s) {
+    const int tap = s / CB, cb = s - tap * CB;
+    const int ky = tap / a.ksize, kx = tap - ky * a.ksize;
+#pragma unroll
+    for (int i = 0; i < XI; ++i) {
+      const int h = ph[i] + ky, w = pw[i] + kx;
+      if ((unsigned)h < (unsigned)a.H && (unsigned)w < (unsigned)a.W) {
+        const size_t off = (size_t)(pbase[i] + ky * a.W + kx) * a.Cin + cb * kKT + 4 * c4;
+        xr[i] = *reinterpret_cast<const f32x4*>(a.x + off);
+      } else {
+        xr[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+      }
+    }
+    const uint4* wsrc = a.wp + (size_t)s * (a.Cout * 8);
+#pragma unroll
+    for (int i = 0; i < WI; ++i) {
+      const int q = tid + kThreads * i;
+      const int plane = q / (NT * 4), co = (q >> 2) % NT, ch = q & 3;
+      wr[i] = wsrc[plane * (a.Cout * 4) + (n0 + co) * 4 + ch];
+    }
+  };
+
+  auto counted = [&](int t) { return t == a.pad || (a.stride == 2 && a.ksize == 3 && t == 2); };
+
+  auto store = [&](int s, _Float16* buf) {
+    const int tap = s / CB, ky = tap / a.ksize, kx = tap - ky * a.ksize;
+    const bool count = blockIdx.y == 0 && counted(ky) && counted(kx);   // (every Cout slice reads the same inputs: count in one)
+    _Float16* xh = buf;
+    _Float16* xl = buf + kXPlane;
+    _Float16* wb = buf + 2 * kXPlane;
+#pragma unroll
+    for (int i = 0; i < XI; ++i) {
+      half4 hi, lo;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        float v = xr[i][e];
+        if (a.relu_in) v = v < 0.0f ? 0.0f : v;          // (keeps NaN: it is counted below)
+        const float y = v * kActScale;
+        bad += (count && !(fabsf(y) <= kF16Max)) ? 1 : 0;  // (the padding's zeros pass)
+        const float c = fminf(fmaxf(y, -kF16Max), kF16Max);
+        const _Float16 h = (_Float16)c;
+        hi[e] = h;
+        lo[e] = (_Float16)(c - (float)h);
+      }
+      const int p = (tid >> 3) + 64 * i;
+      const int o = swz(p, c4 >> 1) + 4 * (c4 & 1);
+      *reinterpret_cast<half4*>(xh + o) = hi;
+      *reinterpret_cast<half4*>(xl + o) = lo;
+    }
+#pragma unroll
+    for (int i = 0; i < WI; ++i) {
+      const int q = tid + kThreads * i;
+      const int plane = q / (NT * 4), co = (q >> 2) % NT, ch = q & 3;
+      *reinterpret_cast<uint4*>(wb + plane * kWPlane + swz(co, ch)) = wr[i];
+    }
+  };
+
+  f32x4 acc[TI][TJ], accx[TI][TJ];      // hi*hi, and the two cross terms apart
+#pragma unroll
+  for (int i = 0; i < TI; ++i)
+#pragma unroll
+    for (int j = 0; j < TJ; ++j) acc[i][j] = accx[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+  load(0);
+  store(0, lds);
+  __syncthreads();
+  const int fr = lane & 15, fc = lane >> 4;
+  for (int s = 0; s < steps; ++s) {
+    _Float16* cur = lds + (s & 1) * kBufHalves;
+    if (s + 1 < steps) load(s + 1);
+    const _Float16* xh = cur;
+    const _Float16* xl = cur + kXPlane;
+    const _Float16* wh = cur + 2 * kXPlane;
+    const _Float16* wl = wh + kWPlane;
+    if constexpr (TJ >= TI) {             // all activation fragments held, weight fragments streamed (Big)
+      half8 bh[TI], bl[TI];
+#pragma unroll
+      for (int i = 0; i < TI; ++i) {
+        const int o = swz(wm * TI * 16 + i * 16 + fr, fc);
+        bh[i] = *reinterpret_cast<const half8*>(xh + o);
+        bl[i] = *reinterpret_cast<const half8*>(xl + o);
+      }
+#pragma unroll
+      for (int j = 0; j < TJ; ++j) {
+        const int o = swz(wn * TJ * 16 + j * 16 + fr, fc);
+        const half8 ah = *reinterpret_cast<const half8*>(wh + o);
+        const half8 al = *reinterpret_cast<const half8*>(wl + o);
+#pragma unroll
+        for (int i = 0; i < TI; ++i) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bh[i], acc[i][j], 0, 0, 0);
+#pragma unroll
+        for (int i = 0; i < TI; ++i) accx[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bl[i], accx[i][j], 0, 0, 0);
+#pragma unroll
+        for (int i = 0; i < TI; ++i) accx[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(al, bh[i], accx[i][j], 0, 0, 0);
+      }
+    } else {                              // the other way round (Mid, Narrow): 24 fragment VGPRs instead of 40, inside 128
+      half8 ah[TJ], al[TJ];
+#pragma unroll
+      for (int j = 0; j < TJ; ++j) {
+        const int o = swz(wn * TJ * 16 + j * 16 + fr, fc);
+        ah[j] = *reinterpret_cast<const half8*>(wh + o);
+        al[j] = *reinterpret_cast<const half8*>(wl + o);
+      }
+#pragma unroll
+      for (int i = 0; i < TI; ++i) {
+        const int o = swz(wm * TI * 16 + i * 16 + fr, fc);
+        const half8 bh = *reinterpret_cast<const half8*>(xh + o);
+        const half8 bl = *reinterpret_cast<const half8*>(xl + o);
+#pragma unroll
+        for (int j = 0; j < TJ; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[j], bh, acc[i][j], 0, 0, 0);
+#pragma unroll
+        for (int j = 0; j < TJ; ++j) accx[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[j], bl, accx[i][j], 0, 0, 0);
+#pragma unroll
+        for (int j = 0; j < TJ; ++j) accx[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(al[j], bh, accx[i][j], 0, 0, 0);
+      }
+    }
+    if (s + 1 < steps) store(s + 1, lds + ((s + 1) & 1) * kBufHalves);
+    __syncthreads();
+  }
+
+  // epilogue: D[co][px] -- lane holds pixel fr of each 16-pixel tile and channels 4*fc .. 4*fc+3 of each 16-channel tile
+#pragma unroll
+  for (int j = 0; j < TJ; ++j) {
+    const int co = n0 + wn * TJ * 16 + j * 16 + 4 * fc;
+    const f32x4 us = *reinterpret_cast<const f32x4*>(a.unscale + co) * kActUnscale;
+    const f32x4 b = a.shift ? *reinterpret_cast<const f32x4*>(a.shift + co) : f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int i = 0; i < TI; ++i) {
+      const int m = m0 + wm * TI * 16 + i * 16 + fr;
+      if (m >= a.M) continue;
+      const size_t off = (size_t)m * a.Cout + co;
+      f32x4 v = (acc[i][j] + accx[i][j]) * us + b;
+      if (a.res) v += *reinterpret_cast<const f32x4*>(a.res + off);
+      if (a.relu_out) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) v[e] = v[e] < 0.0f ? 0.0f : v[e];
+      }
+      if (!a.out2)
+        *reinterpret_cast<f32x4*>(a.out + off) = v;
+      else if (co < a.csplit)         // (csplit % 4 == 0: a lane's 4 channels fall on one side)
+        *reinterpret_cast<f32x4*>(a.out + (size_t)m * a.csplit + co) = v;
+      else
+        *reinterpret_cast<f32x4*>(a.out2 + (size_t)m * (a.Cout - a.csplit) + (co - a.csplit)) = v;
+    }
+  }
+  if (a.range && bad) atomicAdd(a.range, bad);
+}
+
+template <int WM, int WN, int TI, int TJ, int WPE>
+void launch(const SplitArgs& a, hipStream_t st) {
+  constexpr int MT = WM * TI * 16, NT = WN * TJ * 16;
+  hipLaunchKernelGGL((conv_split<WM, WN, TI, TJ, WPE>), dim3((unsigned)((a.M + MT - 1) / MT), (unsigned)(a.Cout / NT)), dim3(kThreads),
+                     0, st, a);
+}
+
+}  // namespace
+}  // namespace rmnet
+
+extern "C" int rmnet_conv_split_f32(const float* x, const void* wpack, const float* w_unscale, const float* shift,
+                                    const float* res, int flags, int N, int H, int W, int Cin, int Cout, int ksize, int stride,
+                                    float* out, float* out2, int out_split, int32_t* range_word, void* stream) {
+  using namespace rmnet;
+  if (!x || !wpack || !w_unscale || !out || N <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0) return RMNET_E_INVALID_ARG;
+  if (flags & ~(RMNET_CONV_RELU_IN | RMNET_CONV_RELU_OUT)) return RMNET_E_INVALID_ARG;
+  if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(wpack) | reinterpret_cast<uintptr_t>(w_unscale) |
+       reinterpret_cast<uintptr_t>(shift) | reinterpret_cast<uintptr_t>(res) | reinterpret_cast<uintptr_t>(out) |
+       reinterpret_cast<uintptr_t>(out2)) & 15)
+    return RMNET_E_INVALID_ARG;
+  if (out2 && (res || out_split <= 0 || out_split >= Cout || out_split % 4)) return RMNET_E_INVALID_ARG;
+  if ((ksize != 1 && ksize != 3) || (stride != 1 && stride != 2)) return RMNET_E_UNSUPPORTED;
+  if (Cin % kKT || Cout % 64) return RMNET_E_UNSUPPORTED;
+  const int pad = ksize / 2;
+  const int Ho = (H + 2 * pad - ksize) / stride + 1, Wo = (W + 2 * pad - ksize) / stride + 1;
+  const long long Mi = (long long)N * H * W, M = (long long)N * Ho * Wo;
+  if (Mi * Cin >= (1LL << 31) || M * Cout >= (1LL << 31)) return RMNET_E_UNSUPPORTED;   // (int pixel index, size_t offsets)
+  // out must not overlap x (other workgroups read the same input pixels); it may BE res (each element is read, then written, by
+  // one thread)
+  const char* xb = reinterpret_cast<const char*>(x);
+  const char* ob = reinterpret_cast<const char*>(out);
+  const long long c1 = out2 ? out_split : Cout;
+  if (ob < xb + Mi * Cin * sizeof(float) && xb < ob + M * c1 * sizeof(float)) return RMNET_E_INVALID_ARG;
+  if (out2) {
+    const char* o2 = reinterpret_cast<const char*>(out2);
+    if (o2 < xb + Mi * Cin * sizeof(float) && xb < o2 + M * (Cout - c1) * sizeof(float)) return RMNET_E_INVALID_ARG;
+    if (o2 < ob + M * c1 * sizeof(float) && ob < o2 + M * (Cout - c1) * sizeof(float)) return RMNET_E_INVALID_ARG;
+  }
+  SplitArgs a;
+  a.x = x; a.wp = reinterpret_cast<const uint4*>(wpack); a.unscale = w_unscale; a.shift = shift; a.res = res; a.out = out; a.out2 = out2;
+  a.range = range_word; a.M = (int)M; a.H = H; a.W = W; a.Ho = Ho; a.Wo = Wo; a.Cin = Cin; a.Cout = Cout; a.csplit = (int)c1;
+  a.ksize = ksize; a.stride = stride; a.pad = pad;
+  a.relu_in = (flags & RMNET_CONV_RELU_IN) != 0;
+  a.relu_out = (flags & RMNET_CONV_RELU_OUT) != 0;
+  hipStream_t st = (hipStream_t)stream;
+  if (Cout % 256 == 0 && (M + 127) / 128 * (Cout / 256) >= 512)
+    launch<2, 4, 4, 4, 2>(a, st);     // Big    128 x 256
+  else if (Cout % 128 == 0)
+    launch<2, 4, 4, 2, 4>(a, st);     // Mid    128 x 128
+  else
+    launch<4, 2, 2, 2, 4>(a, st);     // Narrow 128 x 64
+  return check_launch();
+}

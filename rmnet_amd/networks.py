@@ -54,8 +54,18 @@ class _Bottleneck(nn.Module):
 
     def _forward_fused(self, x):
         """Same block with BatchNorm(eval) / skip add / ReLU fused into one pass per convolution
-        (rmnet_channel_affine_f32): 3 elementwise kernels instead of 7-8."""
+        (rmnet_channel_affine_f32): 3 elementwise kernels instead of 7-8.  On a channels-last run every convolution runs on the
+        split-fp16 kernel (csrc/conv_split.hip) instead, BatchNorm folded into its pack, shift / skip / ReLU in its epilogue."""
         from . import ops
+        if _split_path_ok(self, x, self.conv1, ('split',)):
+            x = x.contiguous(memory_format=torch.channels_last)
+            rw = ops.conv_range_word(x.device)
+            t = ops.conv_split(x, self._wp1, self._wu1, self._b1, ksize=1, relu_out=True, range_word=rw)
+            t = ops.conv_split(t, self._wp2, self._wu2, self._b2, ksize=3, stride=self.conv2.stride[0], relu_out=True, range_word=rw)
+            if self.downsample is None:
+                return ops.conv_split(t, self._wp3, self._wu3, self._b3, res=x, ksize=1, relu_out=True, range_word=rw)
+            d = ops.conv_split(x, self._wpd, self._wud, self._bd, ksize=1, stride=self.downsample[0].stride[0], range_word=rw)
+            return ops.conv_split(t, self._wp3, self._wu3, self._b3, res=d, ksize=1, relu_out=True, out=d, range_word=rw)
         t = self.conv1(x)
         ops.channel_affine(t, self._s1, self._b1, relu=True, out=t)
         t = self.conv2(t)
@@ -242,19 +252,20 @@ class Decoder(nn.Module):
 
 
 def split_conv_backend():
-    """'split' (default): the fused decoder convolutions run on csrc/conv3x3.hip; RMNET_CONV=miopen keeps them on MIOpen
-    (A/B switch, read at every call)."""
+    """RMNET_CONV (A/B switch, read at every call): 'split' (default) -- the fused path's trunk, key / value and decoder
+    convolutions run on the split-fp16 kernels (csrc/conv_split.hip, csrc/conv3x3.hip); 'decoder' -- only the decoder's;
+    'miopen' -- none of them."""
     import os
     v = os.environ.get('RMNET_CONV', 'split').lower()
-    if v not in ('split', 'miopen'):
-        raise RuntimeError('RMNET_CONV must be split or miopen, got %r' % v)
+    if v not in ('split', 'decoder', 'miopen'):
+        raise RuntimeError('RMNET_CONV must be split, decoder or miopen, got %r' % v)
     return v
 
 
-def _split_conv_ok(m, x, conv):
-    """The split-fp16 convolution (csrc/conv3x3.hip) serves ``conv`` of module ``m`` on input ``x``: fused epilogues on, eval, a CUDA
-    fp32 4-D input in a channels-last run (the input or the network's weights channels-last), 3x3 / stride 1 / pad 1, 256 outputs,
-    Cin % 32 == 0, and the packed weights present.  Everything else keeps the MIOpen path."""
+def _split_path_ok(m, x, conv, backends):
+    """Module ``m`` may run its convolutions on a split-fp16 kernel for input ``x``: fused epilogues on, packs present and allowed
+    (``m._conv_split``), eval, a CUDA fp32 4-D input with ``conv``'s channels in a channels-last run (the input or the network's
+    weights channels-last), and RMNET_CONV one of ``backends``.  Everything else keeps the MIOpen path."""
     if not (getattr(m, '_fused', False) and getattr(m, '_conv_split', False)) or m.training:
         return False
     if not (x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and x.shape[1] == conv.in_channels):
@@ -262,17 +273,32 @@ def _split_conv_ok(m, x, conv):
     if not (x.is_contiguous(memory_format=torch.channels_last) and not x.is_contiguous()
             or conv.weight.is_contiguous(memory_format=torch.channels_last) and not conv.weight.is_contiguous()):
         return False
+    return split_conv_backend() in backends
+
+
+def _split_conv_ok(m, x, conv):
+    """The decoder's split-fp16 convolution (csrc/conv3x3.hip) serves ``conv`` of module ``m`` on input ``x``: ``_split_path_ok``,
+    3x3 / stride 1 / pad 1, 256 outputs, Cin % 32 == 0."""
     if conv.kernel_size != (3, 3) or conv.stride != (1, 1) or conv.padding != (1, 1) or conv.dilation != (1, 1) or conv.groups != 1:
         return False
-    return conv.out_channels == 256 and conv.in_channels % 32 == 0 and split_conv_backend() == 'split'
+    return conv.out_channels == 256 and conv.in_channels % 32 == 0 and _split_path_ok(m, x, conv, ('split', 'decoder'))
+
+
+def split_eligible(conv):
+    """``conv`` (an nn.Conv2d) is a shape rmnet_conv_split_f32 implements: fp32, kernel 1x1 or 3x3 with padding k // 2, stride 1 or
+    2, no dilation or groups, Cin % 32 == 0, Cout % 64 == 0."""
+    k = conv.kernel_size
+    return (isinstance(conv, nn.Conv2d) and conv.weight.dtype == torch.float32 and k in ((1, 1), (3, 3))
+            and conv.padding == (k[0] // 2, k[0] // 2) and conv.stride in ((1, 1), (2, 2)) and conv.dilation == (1, 1)
+            and conv.groups == 1 and conv.in_channels % 32 == 0 and conv.out_channels % 64 == 0)
 
 
 def set_split_conv_(module, enable):
-    """Allow (True) or forbid (False) the split-fp16 decoder convolutions in ``module``'s fused path; returns the previous
-    state of every module touched, for ``restore_split_conv_``."""
+    """Allow (True) or forbid (False) the split-fp16 convolutions (trunks, key / value heads, decoder) in ``module``'s fused path;
+    returns the previous state of every module touched, for ``restore_split_conv_``."""
     prev = {}
     for m in module.modules():
-        if isinstance(m, (ResBlock, Refine, Decoder)):
+        if isinstance(m, (_Bottleneck, KeyValue, ResBlock, Refine, Decoder)):
             prev[m] = getattr(m, '_conv_split', False)
             m._conv_split = bool(enable) and getattr(m, '_wu', getattr(m, '_wu1', None)) is not None
     return prev
@@ -292,6 +318,12 @@ class KeyValue(nn.Module):
         self.value_conv = nn.Conv2d(indim, valdim, 3, padding=1)
 
     def forward(self, x):
+        if _split_path_ok(self, x, self.key_conv, ('split',)):
+            # both heads in ONE launch of the split-fp16 kernel over the concatenated [key | value] pack, written as two tensors
+            from . import ops
+            x = x.contiguous(memory_format=torch.channels_last)
+            return ops.conv_split(x, self._wp, self._wu, self._bkv, ksize=3, range_word=ops.conv_range_word(x.device),
+                                  split=self.key_conv.out_channels)
         return self.key_conv(x), self.value_conv(x)
 
 
@@ -367,6 +399,11 @@ def _bn_scale_shift(bn):
     return scale, bn.bias - bn.running_mean * scale
 
 
+def _bn_scale64(bn):
+    """The eval BatchNorm's per-channel scale in float64 (what conv_split_pack folds into the weights)."""
+    return bn.weight.double() / torch.sqrt(bn.running_var.double() + bn.eps)
+
+
 def _fold(conv, bn):
     scale, shift = _bn_scale_shift(bn)
     fused = nn.Conv2d(conv.in_channels, conv.out_channels, conv.kernel_size, conv.stride, conv.padding,
@@ -431,6 +468,32 @@ def fuse_epilogues_(module, enable=True):
                 sc, sh = _bn_scale_shift(m.downsample[1])
                 put(m, '_sd', sc.contiguous())
                 put(m, '_bd', sh.contiguous())
+            # packed split-fp16 weights with the BatchNorm scale folded in (csrc/conv_split.hip); 1-D, so .to(memory_format=...)
+            # leaves them.  The shifts are the _b* above.
+            from . import ops
+            convs = [('1', m.conv1, m.bn1), ('2', m.conv2, m.bn2), ('3', m.conv3, m.bn3)]
+            if m.downsample is not None:
+                convs.append(('d', m.downsample[0], m.downsample[1]))
+            ok = all(split_eligible(c) for _, c, _ in convs)
+            for suffix, c, bn in convs:
+                wp, wu = ops.conv_split_pack(c.weight, _bn_scale64(bn)) if ok else (None, None)
+                put(m, '_wp' + suffix, wp)
+                put(m, '_wu' + suffix, wu)
+            m._conv_split = ok and enable
+        elif isinstance(m, KeyValue):
+            from . import ops
+            kc, vc = m.key_conv, m.value_conv
+            ok = (split_eligible(kc) and split_eligible(vc) and kc.kernel_size == vc.kernel_size == (3, 3)
+                  and kc.stride == vc.stride == (1, 1) and kc.in_channels == vc.in_channels
+                  and kc.bias is not None and vc.bias is not None)
+            wp = wu = bkv = None
+            if ok:
+                wp, wu = ops.conv_split_pack(torch.cat((kc.weight, vc.weight)))
+                bkv = torch.cat((kc.bias, vc.bias)).contiguous()
+            put(m, '_wp', wp)
+            put(m, '_wu', wu)
+            put(m, '_bkv', bkv)
+            m._conv_split = ok and enable
         elif isinstance(m, (EncoderMemory, EncoderQuery)):
             sc, sh = _bn_scale_shift(m.bn1)
             put(m, '_s1', sc.contiguous())
@@ -462,7 +525,7 @@ def fuse_epilogues_(module, enable=True):
                 snapshot(mod)
 
     for m in module.modules():
-        if isinstance(m, (_Bottleneck, EncoderMemory, EncoderQuery, ResBlock, Refine, Decoder)):
+        if isinstance(m, (_Bottleneck, KeyValue, EncoderMemory, EncoderQuery, ResBlock, Refine, Decoder)):
             m._fused = bool(enable)
             snapshot(m)
             handle = getattr(m, '_fuse_hook', None)

@@ -620,6 +620,95 @@ def conv3x3_split(x, wpack, w_unscale, bias=None, res=None, relu_in=False, relu_
     return out
 
 
+@torch.no_grad()
+def conv_split_pack(weight, bn_scale=None):
+    """[Cout, Cin, k, k] fp32 weight (k = 1 or 3, Cin % 32 == 0, Cout % 64 == 0), optionally times a per-output-channel
+    ``bn_scale`` (a folded BatchNorm: the product is formed in float64) -> (wpack [k*k * Cin * Cout * 2] fp16 bits as int16,
+    w_unscale fp32 [Cout]) in the layout of include/rmnet_hip.h (rmnet_conv_split_f32): per output channel a power-of-two scale
+    2^e puts max |w * bn_scale| in [2^14, 2^15), the scaled product is split into fp16 hi = rne(ws), lo = rne(ws - hi) and laid
+    out as [tap][Cin / 32][hi, lo][co][Cin % 32].  hi + lo, unscaled, is w * bn_scale to ~2^-22 relative."""
+    if weight.dim() != 4 or weight.shape[2] != weight.shape[3] or weight.shape[2] not in (1, 3) or weight.shape[1] % 32 \
+            or weight.shape[0] % 64:
+        raise RuntimeError('conv_split_pack needs a [Cout, Cin, k, k] weight with k in (1, 3), Cin % 32 == 0 and Cout % 64 == 0, '
+                           'got %s' % (tuple(weight.shape),))
+    if weight.dtype != torch.float32:
+        raise RuntimeError('conv_split_pack needs fp32 weights, got %s' % weight.dtype)
+    cout, cin, k = weight.shape[0], weight.shape[1], weight.shape[2]
+    w = weight.detach().double()
+    if bn_scale is not None:
+        if bn_scale.numel() != cout:
+            raise RuntimeError('bn_scale must have Cout = %d elements' % cout)
+        w = w * bn_scale.detach().to(w.device, torch.float64).view(-1, 1, 1, 1)
+    amax = w.abs().amax(dim=(1, 2, 3))
+    _, ex = torch.frexp(amax)                              # amax in [2^(ex-1), 2^ex)
+    e = torch.where(amax > 0, 15 - ex, torch.zeros_like(ex))
+    ws = torch.ldexp(w, e.view(-1, 1, 1, 1).to(w.dtype))   # exact: power-of-two scaling
+    hi = ws.half()
+    lo = (ws - hi.double()).half()
+    planes = torch.stack([p.reshape(cout, cin // 32, 32, k * k).permute(3, 1, 0, 2) for p in (hi, lo)], dim=2)
+    unscale = torch.ldexp(torch.ones_like(amax), (-e).to(amax.dtype)).float()
+    return planes.contiguous().view(-1).view(torch.int16), unscale.contiguous()
+
+
+def conv_split(x, wpack, w_unscale, shift=None, res=None, ksize=3, stride=1, relu_in=False, relu_out=False, out=None,
+               range_word=None, split=None):
+    """act(conv(pre(x), w) + shift + res) for a channels-last fp32 ``x`` [N, Cin, H, W], kernel ``ksize`` (1 or 3, padding
+    ksize // 2), ``stride`` (1 or 2) and Cout = ``w_unscale.numel()`` (a multiple of 64) on the split-fp16 MFMA kernel
+    (csrc/conv_split.hip); ``pre`` / ``act`` = ReLU when ``relu_in`` / ``relu_out``.  ``wpack, w_unscale`` come from
+    ``conv_split_pack``.  ``out`` (channels-last, may be ``res``, must not be ``x``) defaults to a new tensor.  ``range_word``: as
+    for ``conv3x3_split``.  ``split`` (a multiple of 4 inside (0, Cout), no ``res`` / ``out``): the output channels [0, split) and
+    [split, Cout) are written to two new channels-last tensors, returned as a pair.  No fall-back: anything else is a
+    RuntimeError."""
+    _check_act(x, 'x')
+    if x.dim() != 4 or not x.is_contiguous(memory_format=torch.channels_last):
+        raise RuntimeError('x must be a channels-last [N, Cin, H, W] tensor')
+    if ksize not in (1, 3) or stride not in (1, 2):
+        raise RuntimeError('conv_split implements ksize 1 / 3 and stride 1 / 2, got %r / %r' % (ksize, stride))
+    N, cin, H, W = x.shape
+    _check(w_unscale, 'w_unscale')
+    cout = w_unscale.numel()
+    if cin % 32 or cout % 64 or cout == 0:
+        raise RuntimeError('conv_split needs Cin % 32 == 0 and Cout % 64 == 0, got %d, %d' % (cin, cout))
+    _check(wpack, 'wpack', torch.int16)
+    if wpack.numel() != ksize * ksize * cin * cout * 2:
+        raise RuntimeError('wpack has %d elements, a %dx%d Cin = %d Cout = %d pack has %d'
+                           % (wpack.numel(), ksize, ksize, cin, cout, ksize * ksize * cin * cout * 2))
+    pad = ksize // 2
+    shape = (N, cout, (H + 2 * pad - ksize) // stride + 1, (W + 2 * pad - ksize) // stride + 1)
+    if shift is not None:
+        _check(shift, 'shift')
+        if shift.numel() != cout:
+            raise RuntimeError('shift must have Cout = %d elements' % cout)
+    if res is not None:
+        _check_act(res, 'res')
+        if tuple(res.shape) != shape or not res.is_contiguous(memory_format=torch.channels_last):
+            raise RuntimeError('res must be a channels-last %s tensor' % (shape,))
+    out2 = None
+    if split is not None:
+        if res is not None or out is not None or not 0 < split < cout or split % 4:
+            raise RuntimeError('conv_split: split must be a multiple of 4 in (0, %d), without res / out' % cout)
+        out = torch.empty((N, split) + shape[2:], dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
+        out2 = torch.empty((N, cout - split) + shape[2:], dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
+    elif out is None:
+        out = torch.empty(shape, dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
+    else:
+        _check_act(out, 'out')
+        if tuple(out.shape) != shape or not out.is_contiguous(memory_format=torch.channels_last):
+            raise RuntimeError('out must be a channels-last %s tensor' % (shape,))
+    if range_word is not None:
+        _check(range_word, 'range_word', torch.int32)
+    for t in (wpack, w_unscale, shift, res, out, range_word):
+        if t is not None and t.device != x.device:
+            raise RuntimeError('conv_split: every tensor must be on %s' % x.device)
+    flags = (CONV_RELU_IN if relu_in else 0) | (CONV_RELU_OUT if relu_out else 0)
+    lib = _lib.load()
+    with torch.cuda.device(x.device):
+        rc = lib.rmnet_conv_split_f32(_ptr(x), _ptr(wpack), _ptr(w_unscale), _ptr(shift), _ptr(res), flags, N, H, W, cin, cout,
+                                      ksize, stride, _ptr(out), _ptr(out2), split or 0, _ptr(range_word), _stream(x.device))
+    _lib.check(rc, 'rmnet_conv_split_f32')
+    return out if out2 is None else (out, out2)
+
+
 def affine_relu_maxpool(x, scale=None, shift=None):
     """max_pool2d(relu(x * scale[c] + shift[c]), 3, stride=2, padding=1) in one pass (csrc/epilogue.hip):
     the ResNet stem's bn1 -> relu -> maxpool without the full-resolution intermediate."""

@@ -363,8 +363,9 @@ class RMNet(nn.Module):
         (the bank's slot / frame count travel as a device counter): with ``commit=False`` the step can be captured
         into a HIP graph once and replayed for every frame (``forward`` does).
 
-        After ``fuse_epilogues()`` on a channels-last network the decoder's 256-channel convolutions run on the split-fp16 kernel,
-        which saturates activations outside |x| < 1023.5 and counts them in ``ops.conv_range_word(device)``.  ``forward``
+        After ``fuse_epilogues()`` on a channels-last network the ResNet-50 trunks' bottleneck convolutions, the key / value heads and
+        the decoder's 256-channel convolutions run on the split-fp16 kernels (``RMNET_CONV=decoder``: the decoder's only), which
+        saturate activations outside |x| < 1023.5 and count them in ``ops.conv_range_word(device)``.  ``forward``
         zeroes and checks that word once per clip and redoes the clip on MIOpen when it is non-zero; a streaming caller of
         ``frame_step`` must do the same itself (zero it, read it at its own sync point, redo with
         ``networks.set_split_conv_(net, False)``)."""
@@ -422,8 +423,10 @@ class RMNet(nn.Module):
         commit = set(range(0, N, memorize_every)) | fresh
         ctx = self._ClipContext(self, B, K, H, W, n_max, dev)
         bank = self.new_bank(ctx, sum(1 for j in commit if j <= N - 2) + 1, exact=_exact, precision=_precision)
-        # the split-fp16 decoder convolutions count activations outside their window here (read with the bank's status)
-        conv_word = ops.conv_range_word(dev) if getattr(self.decoder, '_conv_split', False) and getattr(self.decoder, '_fused', False) else None
+        # the split-fp16 convolutions (trunks, key / value heads, decoder) count activations outside their window here (read with the
+        # bank's status)
+        split = any(getattr(m, '_conv_split', False) and getattr(m, '_fused', False) for m in self.modules())
+        conv_word = ops.conv_range_word(dev) if split else None
         if conv_word is not None:
             conv_word.zero_()
 
