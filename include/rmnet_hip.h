@@ -316,6 +316,33 @@ int rmnet_conv_split_f32(const float *x, const void *wpack, const float *w_unsca
                          int N, int H, int W, int Cin, int Cout, int ksize, int stride, float *out, float *out2, int out_split,
                          int32_t *range_word, void *stream);
 
+/* C1 encoder stems (additive export, same ABI version): the 7x7 / stride 2 / pad 3 stem convolution, the folded BatchNorm, ReLU and
+ * MaxPool2d(3, stride 2, padding 1) in ONE launch (csrc/stem.hip), on the split-fp16 arithmetic of rmnet_conv3x3_split_f32; the
+ * half-resolution 64-channel activation is never written.  Replaces conv1 (+ conv1_m + conv1_o) / bn1 / relu / maxpool of both
+ * encoders (models/rmnet.py:66-76, 96-100) and the 5-channel concatenation in front of the memory encoder's stem.
+ *   frame [N, 3, H, W] fp32 NCHW; mask, other [N, H, W] fp32, both may be NULL.  mask NULL: Cin = 3 (query encoder; other must be
+ *         NULL too).  mask given: Cin = 5, input channels (frame 0..2, mask, other); other NULL = an all-zero fifth plane;
+ *   out   [N, Hp, Wp, 64] fp32 (channels-last) = max_pool(relu(conv(x) * g + shift[co])), Hc = (H - 1) / 2 + 1, Hp = (Hc - 1) / 2 + 1
+ *         (Wc, Wp alike); any H, W >= 1.  Pool padding counts as -inf; a NaN in a window gives NaN (as rmnet_affine_relu_maxpool_f32);
+ *   shift [64] may be NULL; g is folded into the pack;
+ *   range_word: as above; every INPUT element (of the planes given) with |x| >= 1023.5, NaN or Inf is saturated and counted once.
+ * wpack, w_unscale, shift and out 16-byte aligned.  RMNET_E_UNSUPPORTED only for N*3*H*W or N*Hp*Wp*64 >= 2^31.
+ *
+ * Weight pack (rmnet_amd.ops.stem_pack) for w [64][Cin][7][7] fp32, Cin = 3 or 5 (the memory encoder: conv1 | conv1_m | conv1_o
+ * stacked along Cin), and an optional per-channel factor g [64]:
+ *   wg, e[co], ws, hi, lo, w_unscale: as for rmnet_conv_split_f32;
+ *   k              = (7 * ky + kx) * Cin + ci, 0 <= k < 49 * Cin, zero-padded to Kp = 160 (Cin 3: 147) or 256 (Cin 5: 245);
+ *   wpack          fp16 [Kp / 32][2][64][32]: [k / 32][plane: hi, lo][co][k % 32]  (Kp * 64 * 2 * 2 bytes). */
+int rmnet_stem_split_f32(const float *frame, const float *mask, const float *other, const void *wpack, const float *w_unscale,
+                         const float *shift, int N, int H, int W, float *out, int32_t *range_word, void *stream);
+
+/* C1 decoder prediction head (additive export, same ABI version): out = conv3x3_p1(relu(x), w) + bias with two output channels in
+ * plain fp32 FMA (csrc/pred_head.hip).  Replaces F.relu(m2), Decoder.pred2 (models/rmnet.py:138-139) and the layout copy behind it.
+ *   x    [n, Hq, Wq, C] fp32 (channels-last), C % 32 == 0, 16-byte aligned;  w [2][C][3][3], bias [2] fp32 (no pack);
+ *   out  [n, 2, Hq, Wq] fp32 NCHW.
+ * No window and no range word.  RMNET_E_UNSUPPORTED for C % 32 != 0 or n*Hq*Wq*C >= 2^31. */
+int rmnet_pred_head_f32(const float *x, const float *w, const float *bias, int n, int Hq, int Wq, int C, float *out, void *stream);
+
 /* P3/P4 tail: decoder logits -> foreground probability -> soft aggregation -> un-pad (-> soft-max over
  * the K mask channels) in one pass.  dec [n_tot,2,Hp,Wp]: 2-class logits of the objects in flight;
  * clip b owns objects [obj_begin[b], obj_begin[b+1]) (device int32 [B+1]); logit / prob [B,K,H,W] with

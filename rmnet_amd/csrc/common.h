@@ -13,6 +13,7 @@
 #error "librmnet_hip is written for gfx950 (MI355X): build with --offload-arch=gfx950"
 #endif
 constexpr int kLdsBytesPerCU = 160 * 1024;
+constexpr int kNumCUs = 256;               // MI355X; sizes the grids of the persistent kernels (stem.hip), not correctness
 
 namespace rmnet {
 

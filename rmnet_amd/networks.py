@@ -57,7 +57,7 @@ class _Bottleneck(nn.Module):
         (rmnet_channel_affine_f32): 3 elementwise kernels instead of 7-8.  On a channels-last run every convolution runs on the
         split-fp16 kernel (csrc/conv_split.hip) instead, BatchNorm folded into its pack, shift / skip / ReLU in its epilogue."""
         from . import ops
-        if _split_path_ok(self, x, self.conv1, ('split',)):
+        if _split_path_ok(self, x, self.conv1, ('full', 'split', 'trunk')):
             x = x.contiguous(memory_format=torch.channels_last)
             rw = ops.conv_range_word(x.device)
             t = ops.conv_split(x, self._wp1, self._wu1, self._b1, ksize=1, relu_out=True, range_word=rw)
@@ -155,8 +155,17 @@ class EncoderMemory(nn.Module):
         self.res2, self.res3, self.res4 = trunk.layer1, trunk.layer2, trunk.layer3
 
     def forward(self, in_f, in_m, in_o):
+        if _split_path_ok(self, in_f, self.conv1, _stem_backends()):
+            # the whole stem in one launch of the split-fp16 kernel (csrc/stem.hip): the three sources are read in place (no 5-channel
+            # cat), a missing others-mask is an all-zero plane, and the un-pooled activation is never written
+            from . import ops
+            pooled = ops.stem_split(in_f.contiguous(), in_m.float().contiguous(), None if in_o is None else in_o.float().contiguous(),
+                                    self._wp, self._wu, self._b1, range_word=ops.conv_range_word(in_f.device))
+            r2 = self.res2(pooled)
+            r3 = self.res3(r2)
+            return self.res4(r3), r3, r2, None, in_f
         m = in_m.unsqueeze(1).float()
-        o = in_o.unsqueeze(1).float()
+        o = torch.zeros_like(m) if in_o is None else in_o.unsqueeze(1).float()
         if getattr(self, '_fused', False) and not self.training and in_f.is_cuda:
             # conv1(f) + conv1_m(m) + conv1_o(o) is ONE 7x7 convolution over the 5 stacked input
             # channels with the three weights stacked the same way: two convolutions and two
@@ -186,7 +195,11 @@ class EncoderQuery(nn.Module):
         self.res2, self.res3, self.res4 = trunk.layer1, trunk.layer2, trunk.layer3
 
     def forward(self, in_f):
-        if getattr(self, '_fused', False) and not self.training and in_f.is_cuda:
+        if _split_path_ok(self, in_f, self.conv1, _stem_backends()):
+            from . import ops
+            c1, pooled = None, ops.stem_split(in_f.contiguous(), wpack=self._wp, w_unscale=self._wu, shift=self._b1,
+                                              range_word=ops.conv_range_word(in_f.device))      # (csrc/stem.hip: the whole stem)
+        elif getattr(self, '_fused', False) and not self.training and in_f.is_cuda:
             from . import ops
             t = self.conv1(in_f)
             c1, pooled = None, ops.affine_relu_maxpool(t, self._s1, self._b1)   # (c1 not materialised)
@@ -245,20 +258,38 @@ class Decoder(nn.Module):
             m4 = self.ResMM(self.convFM(r4))
         m3 = self.RF3(r3, m4)
         m2 = self.RF2(r2, m3)
+        if _pred_head_ok(self, m2):
+            # ReLU, the two-channel convolution and the NCHW layout of the tail in one kernel (csrc/pred_head.hip)
+            from . import ops
+            p2 = ops.pred_head(m2.contiguous(memory_format=torch.channels_last), self._wpred.view(self.pred2.weight.shape), self.pred2.bias)
+            return F.interpolate(p2, scale_factor=4, mode='bilinear', align_corners=False)
         p2 = self.pred2(F.relu(m2))
         # (channels-last runs: back to NCHW HERE, on the 2-channel quarter-resolution map -- the decoder tail kernel reads NCHW planes, and
         #  converting after the x4 upsample would move 16x the bytes; a no-op for NCHW tensors)
         return F.interpolate(p2.contiguous(), scale_factor=4, mode='bilinear', align_corners=False)
 
 
+# The stem and prediction-head kernels become part of the default path ('split') only on a measured win: per-step time in a kernel
+# trace below the dispatches they replace, and the bench line not below RMNET_CONV=trunk (profiles/r09_a_stem_head.md).  No such
+# measurement exists yet, so both are off by default and RMNET_CONV=full selects them.
+STEM_DEFAULT = False
+HEAD_DEFAULT = False
+
+
+def _stem_backends():
+    return ('full', 'split') if STEM_DEFAULT else ('full',)
+
+
 def split_conv_backend():
-    """RMNET_CONV (A/B switch, read at every call): 'split' (default) -- the fused path's trunk, key / value and decoder
-    convolutions run on the split-fp16 kernels (csrc/conv_split.hip, csrc/conv3x3.hip); 'decoder' -- only the decoder's;
-    'miopen' -- none of them."""
+    """RMNET_CONV (A/B switch, read at every call): 'full' -- every convolution of the fused path runs on a HIP kernel: the stems
+    (csrc/stem.hip), the trunks, key / value heads and the decoder's 256-channel convolutions on the split-fp16 kernels
+    (csrc/conv_split.hip, csrc/conv3x3.hip) and the prediction head (csrc/pred_head.hip); 'trunk' -- all but the stems and the
+    prediction head, which stay on MIOpen; 'split' (default) -- 'trunk' plus whichever of the stem / head kernels STEM_DEFAULT /
+    HEAD_DEFAULT name; 'decoder' -- only the decoder's 256-channel convolutions; 'miopen' -- none of them."""
     import os
     v = os.environ.get('RMNET_CONV', 'split').lower()
-    if v not in ('split', 'decoder', 'miopen'):
-        raise RuntimeError('RMNET_CONV must be split, decoder or miopen, got %r' % v)
+    if v not in ('full', 'split', 'trunk', 'decoder', 'miopen'):
+        raise RuntimeError('RMNET_CONV must be full, split, trunk, decoder or miopen, got %r' % v)
     return v
 
 
@@ -281,7 +312,18 @@ def _split_conv_ok(m, x, conv):
     3x3 / stride 1 / pad 1, 256 outputs, Cin % 32 == 0."""
     if conv.kernel_size != (3, 3) or conv.stride != (1, 1) or conv.padding != (1, 1) or conv.dilation != (1, 1) or conv.groups != 1:
         return False
-    return conv.out_channels == 256 and conv.in_channels % 32 == 0 and _split_path_ok(m, x, conv, ('split', 'decoder'))
+    return conv.out_channels == 256 and conv.in_channels % 32 == 0 and _split_path_ok(m, x, conv, ('full', 'split', 'trunk', 'decoder'))
+
+
+def _pred_head_ok(m, x):
+    """The prediction-head kernel (csrc/pred_head.hip) serves ``m.pred2`` of Decoder ``m`` on input ``x``: ``_split_path_ok`` under
+    RMNET_CONV=full (and =split once HEAD_DEFAULT is set), a flat copy of the weight present, 3x3 / stride 1 / pad 1, two biased outputs, Cin % 32 == 0."""
+    c = m.pred2
+    if getattr(m, '_wpred', None) is None or c.bias is None or c.out_channels != 2 or c.in_channels % 32:
+        return False
+    if c.kernel_size != (3, 3) or c.stride != (1, 1) or c.padding != (1, 1) or c.dilation != (1, 1) or c.groups != 1:
+        return False
+    return _split_path_ok(m, x, c, ('full', 'split') if HEAD_DEFAULT else ('full',))
 
 
 def split_eligible(conv):
@@ -294,11 +336,13 @@ def split_eligible(conv):
 
 
 def set_split_conv_(module, enable):
-    """Allow (True) or forbid (False) the split-fp16 convolutions (trunks, key / value heads, decoder) in ``module``'s fused path;
-    returns the previous state of every module touched, for ``restore_split_conv_``."""
+    """Allow (True) or forbid (False) the HIP convolutions (stems, trunks, key / value heads, decoder, prediction head) in
+    ``module``'s fused path; returns the previous state of every module touched, for ``restore_split_conv_``."""
     prev = {}
     for m in module.modules():
-        if isinstance(m, (_Bottleneck, KeyValue, ResBlock, Refine, Decoder)):
+        if isinstance(m, (_Bottleneck, KeyValue, ResBlock, Refine, Decoder, EncoderMemory, EncoderQuery)):
+            # (one flag per module: an encoder's covers its stem (_wp / _wu), a Decoder's covers convFM (_wp / _wu) AND the prediction
+            #  head, which has no pack -- _pred_head_ok additionally asks for the flat weight copy _wpred)
             prev[m] = getattr(m, '_conv_split', False)
             m._conv_split = bool(enable) and getattr(m, '_wu', getattr(m, '_wu1', None)) is not None
     return prev
@@ -318,7 +362,7 @@ class KeyValue(nn.Module):
         self.value_conv = nn.Conv2d(indim, valdim, 3, padding=1)
 
     def forward(self, x):
-        if _split_path_ok(self, x, self.key_conv, ('split',)):
+        if _split_path_ok(self, x, self.key_conv, ('full', 'split', 'trunk')):
             # both heads in ONE launch of the split-fp16 kernel over the concatenated [key | value] pack, written as two tensors
             from . import ops
             x = x.contiguous(memory_format=torch.channels_last)
@@ -500,6 +544,15 @@ def fuse_epilogues_(module, enable=True):
             put(m, '_b1', sh.contiguous())
             if isinstance(m, EncoderMemory):
                 put(m, '_w5', torch.cat((m.conv1.weight, m.conv1_m.weight, m.conv1_o.weight), dim=1).contiguous())
+            # packed split-fp16 stem (csrc/stem.hip), the BatchNorm scale folded in; the shift is _b1.  _w5 / _s1 stay for the MIOpen path
+            from . import ops
+            w = m._w5 if isinstance(m, EncoderMemory) else m.conv1.weight
+            ok = w.dtype == torch.float32 and tuple(w.shape) in ((64, 3, 7, 7), (64, 5, 7, 7)) and m.conv1.stride == (2, 2) \
+                and m.conv1.padding == (3, 3) and isinstance(m.bn1, nn.BatchNorm2d)
+            wp, wu = ops.stem_pack(w, _bn_scale64(m.bn1)) if ok else (None, None)
+            put(m, '_wp', wp)
+            put(m, '_wu', wu)
+            m._conv_split = ok and enable
         elif isinstance(m, (ResBlock, Refine, Decoder)):
             # packed split-fp16 weights of the 256-channel 3x3 convolutions (csrc/conv3x3.hip); 1-D, so .to(memory_format=...) leaves them
             from . import ops
@@ -514,6 +567,9 @@ def fuse_epilogues_(module, enable=True):
                     wp, wu, ok = None, None, False
                 put(m, '_wp' + suffix, wp)
                 put(m, '_wu' + suffix, wu)
+            if isinstance(m, Decoder):
+                # the prediction head (csrc/pred_head.hip) reads the plain fp32 weight: a flat NCHW copy, which .to(memory_format=...) leaves
+                put(m, '_wpred', m.pred2.weight.detach().contiguous().view(-1).clone() if m.pred2.weight.dtype == torch.float32 else None)
             m._conv_split = ok and enable
 
     def _refresh(mod, incompatible):

@@ -709,6 +709,114 @@ def conv_split(x, wpack, w_unscale, shift=None, res=None, ksize=3, stride=1, rel
     return out if out2 is None else (out, out2)
 
 
+STEM_COUT = 64                    # csrc/stem.hip: output channels of the encoder stems
+
+
+def stem_kp(cin):
+    """Padded K of the stem pack: 49 * Cin rounded up to a multiple of 32 (147 -> 160, 245 -> 256)."""
+    return (49 * cin + 31) // 32 * 32
+
+
+@torch.no_grad()
+def stem_pack(weight, bn_scale=None):
+    """[64, Cin, 7, 7] fp32 stem weight (Cin 3, or 5 = conv1 | conv1_m | conv1_o stacked), optionally times a per-output-channel
+    ``bn_scale`` (the folded BatchNorm: the product is formed in float64) -> (wpack [Kp * 64 * 2] fp16 bits as int16, w_unscale
+    fp32 [64]) in the layout of include/rmnet_hip.h (rmnet_stem_split_f32): scale and hi / lo split as ``conv_split_pack``,
+    K index k = (7 * ky + kx) * Cin + ci zero-padded to Kp = 160 / 256, laid out as [k / 32][hi, lo][co][k % 32]."""
+    if weight.dim() != 4 or weight.shape[0] != STEM_COUT or weight.shape[1] not in (3, 5) or tuple(weight.shape[2:]) != (7, 7):
+        raise RuntimeError('stem_pack needs a [64, Cin, 7, 7] weight with Cin 3 or 5, got %s' % (tuple(weight.shape),))
+    if weight.dtype != torch.float32:
+        raise RuntimeError('stem_pack needs fp32 weights, got %s' % weight.dtype)
+    cin = weight.shape[1]
+    w = weight.detach().double()
+    if bn_scale is not None:
+        if bn_scale.numel() != STEM_COUT:
+            raise RuntimeError('bn_scale must have 64 elements')
+        w = w * bn_scale.detach().to(w.device, torch.float64).view(-1, 1, 1, 1)
+    amax = w.abs().amax(dim=(1, 2, 3))
+    _, ex = torch.frexp(amax)                              # amax in [2^(ex-1), 2^ex)
+    e = torch.where(amax > 0, 15 - ex, torch.zeros_like(ex))
+    ws = torch.ldexp(w, e.view(-1, 1, 1, 1).to(w.dtype))   # exact: power-of-two scaling
+    kp = stem_kp(cin)
+    wk = torch.zeros(STEM_COUT, kp, dtype=torch.float64, device=w.device)
+    wk[:, :49 * cin] = ws.permute(0, 2, 3, 1).reshape(STEM_COUT, 49 * cin)
+    hi = wk.half()
+    lo = (wk - hi.double()).half()
+    planes = torch.stack([p.reshape(STEM_COUT, kp // 32, 32).permute(1, 0, 2) for p in (hi, lo)], dim=1)
+    unscale = torch.ldexp(torch.ones_like(amax), (-e).to(amax.dtype)).float()
+    return planes.contiguous().view(-1).view(torch.int16), unscale.contiguous()
+
+
+def stem_split(frame, mask=None, other=None, wpack=None, w_unscale=None, shift=None, range_word=None):
+    """max_pool2d(relu(conv7x7_s2_p3(x) * g + shift), 3, stride 2, padding 1) in one launch of the split-fp16 stem kernel
+    (csrc/stem.hip) -> channels-last fp32 [N, 64, Hp, Wp].  ``frame`` [N, 3, H, W] NCHW; ``mask`` / ``other`` [N, H, W] (both None:
+    the 3-channel query stem; ``mask`` given: the 5-channel memory stem, ``other`` None = an all-zero plane).  ``wpack, w_unscale``
+    come from ``stem_pack`` (which folds g); ``range_word``: as for ``conv3x3_split``, counted per input element.  No fall-back:
+    anything else is a RuntimeError."""
+    _check(frame, 'frame')
+    if frame.dim() != 4 or frame.shape[1] != 3:
+        raise RuntimeError('frame must be [N, 3, H, W]')
+    N, _, H, W = frame.shape
+    if other is not None and mask is None:
+        raise RuntimeError('stem_split: other without mask')
+    for t, n in ((mask, 'mask'), (other, 'other')):
+        if t is not None:
+            _check(t, n)
+            if tuple(t.shape) != (N, H, W):
+                raise RuntimeError('%s must be [N, H, W] = %s' % (n, (N, H, W)))
+    if wpack is None or w_unscale is None:
+        raise RuntimeError('stem_split needs wpack and w_unscale (ops.stem_pack)')
+    cin = 3 if mask is None else 5
+    _check(wpack, 'wpack', torch.int16)
+    if wpack.numel() != stem_kp(cin) * STEM_COUT * 2:
+        raise RuntimeError('wpack has %d elements, a Cin = %d stem pack has %d' % (wpack.numel(), cin, stem_kp(cin) * STEM_COUT * 2))
+    _check(w_unscale, 'w_unscale')
+    if w_unscale.numel() != STEM_COUT:
+        raise RuntimeError('w_unscale must have 64 elements')
+    if shift is not None:
+        _check(shift, 'shift')
+        if shift.numel() != STEM_COUT:
+            raise RuntimeError('shift must have 64 elements')
+    if range_word is not None:
+        _check(range_word, 'range_word', torch.int32)
+    for t in (mask, other, wpack, w_unscale, shift, range_word):
+        if t is not None and t.device != frame.device:
+            raise RuntimeError('stem_split: every tensor must be on %s' % frame.device)
+    hc, wc = (H - 1) // 2 + 1, (W - 1) // 2 + 1
+    out = torch.empty((N, STEM_COUT, (hc - 1) // 2 + 1, (wc - 1) // 2 + 1), dtype=frame.dtype, device=frame.device,
+                      memory_format=torch.channels_last)
+    lib = _lib.load()
+    with torch.cuda.device(frame.device):
+        rc = lib.rmnet_stem_split_f32(_ptr(frame), _ptr(mask), _ptr(other), _ptr(wpack), _ptr(w_unscale), _ptr(shift), N, H, W,
+                                      _ptr(out), _ptr(range_word), _stream(frame.device))
+    _lib.check(rc, 'rmnet_stem_split_f32')
+    return out
+
+
+def pred_head(x, weight, bias):
+    """conv3x3_p1(relu(x), weight) + bias for a channels-last fp32 ``x`` [n, C, Hq, Wq] (C % 32 == 0) and ``weight`` [2, C, 3, 3],
+    ``bias`` [2] -> NCHW-contiguous [n, 2, Hq, Wq], plain fp32 FMA (csrc/pred_head.hip): the decoder's prediction head with its
+    ReLU and the layout change inside.  No fall-back: anything else is a RuntimeError."""
+    _check_act(x, 'x')
+    if x.dim() != 4 or not x.is_contiguous(memory_format=torch.channels_last):
+        raise RuntimeError('x must be a channels-last [n, C, Hq, Wq] tensor')
+    n, C, H, W = x.shape
+    if C % 32:
+        raise RuntimeError('pred_head needs C %% 32 == 0, got %d' % C)
+    _check(weight, 'weight')
+    _check(bias, 'bias')
+    if tuple(weight.shape) != (2, C, 3, 3) or bias.numel() != 2:
+        raise RuntimeError('pred_head needs weight [2, %d, 3, 3] and bias [2], got %s / %s' % (C, tuple(weight.shape), tuple(bias.shape)))
+    if weight.device != x.device or bias.device != x.device:
+        raise RuntimeError('pred_head: every tensor must be on %s' % x.device)
+    out = torch.empty((n, 2, H, W), dtype=x.dtype, device=x.device)
+    lib = _lib.load()
+    with torch.cuda.device(x.device):
+        rc = lib.rmnet_pred_head_f32(_ptr(x), _ptr(weight), _ptr(bias), n, H, W, C, _ptr(out), _stream(x.device))
+    _lib.check(rc, 'rmnet_pred_head_f32')
+    return out
+
+
 def affine_relu_maxpool(x, scale=None, shift=None):
     """max_pool2d(relu(x * scale[c] + shift[c]), 3, stride=2, padding=1) in one pass (csrc/epilogue.hip):
     the ResNet stem's bn1 -> relu -> maxpool without the full-resolution intermediate."""

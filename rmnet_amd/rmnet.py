@@ -228,7 +228,7 @@ class RMNet(nn.Module):
         (frame, masks), _ = pad_divide_by([frame, masks.float()], 16, (H, W))
         if all(int(n) == 1 for n in n_objects):       # one object per clip: object i IS clip i, nothing to gather
             f_in, m_in = frame, masks[:, 1]
-            o_in = torch.zeros_like(m_in)
+            o_in = None                               # (no other objects: EncoderMemory takes an all-zero plane)
         else:
             fs, ms, os_ = [], [], []
             for b in range(B):
@@ -364,7 +364,10 @@ class RMNet(nn.Module):
         into a HIP graph once and replayed for every frame (``forward`` does).
 
         After ``fuse_epilogues()`` on a channels-last network the ResNet-50 trunks' bottleneck convolutions, the key / value heads and
-        the decoder's 256-channel convolutions run on the split-fp16 kernels (``RMNET_CONV=decoder``: the decoder's only), which
+        the decoder's 256-channel convolutions run on the split-fp16 kernels (``RMNET_CONV=decoder``: the decoder's only); with
+        ``RMNET_CONV=full`` so do the two encoder stems (7x7 convolution, BatchNorm, ReLU and max-pool in one launch), and the
+        prediction head runs on its fp32 kernel (both off by default until measured: ``networks.STEM_DEFAULT / HEAD_DEFAULT``).
+        The split-fp16 kernels
         saturate activations outside |x| < 1023.5 and count them in ``ops.conv_range_word(device)``.  ``forward``
         zeroes and checks that word once per clip and redoes the clip on MIOpen when it is non-zero; a streaming caller of
         ``frame_step`` must do the same itself (zero it, read it at its own sync point, redo with
@@ -423,7 +426,7 @@ class RMNet(nn.Module):
         commit = set(range(0, N, memorize_every)) | fresh
         ctx = self._ClipContext(self, B, K, H, W, n_max, dev)
         bank = self.new_bank(ctx, sum(1 for j in commit if j <= N - 2) + 1, exact=_exact, precision=_precision)
-        # the split-fp16 convolutions (trunks, key / value heads, decoder) count activations outside their window here (read with the
+        # the split-fp16 convolutions (stems, trunks, key / value heads, decoder: any one of them arms the word) count activations outside their window here (read with the
         # bank's status)
         split = any(getattr(m, '_conv_split', False) and getattr(m, '_fused', False) for m in self.modules())
         conv_word = ops.conv_range_word(dev) if split else None
