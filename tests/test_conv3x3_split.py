@@ -12,6 +12,8 @@ import torch.nn.functional as F
 
 from conftest import ROOT
 
+import conv_ref
+
 SRC = os.path.join(ROOT, 'rmnet_amd', 'csrc', 'conv3x3.hip')
 
 
@@ -46,9 +48,7 @@ def _weights(cin, seed=0, std=None):
 
 def _unpack(wp, wu, cin):
     """The pack back to [256, Cin, 3, 3] float64 (hi + lo, unscaled), straight from the documented layout."""
-    p = wp.view(torch.float16).double().view(9, cin // 32, 2, 256, 32)
-    w = (p[:, :, 0] + p[:, :, 1]) * wu.double().view(1, 1, 256, 1)           # [tap][cb][co][kk]
-    return w.permute(2, 1, 3, 0).reshape(256, cin, 3, 3)
+    return conv_ref.unpack_conv_weights(wp, wu, 256, cin, 3)
 
 
 @pytest.mark.parametrize('cin', [64, 256, 1024])

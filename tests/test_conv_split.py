@@ -13,6 +13,8 @@ import torch.nn.functional as F
 
 from conftest import ROOT
 
+import conv_ref
+
 SRC = os.path.join(ROOT, 'rmnet_amd', 'csrc', 'conv_split.hip')
 
 
@@ -47,9 +49,7 @@ def _weights(cout, cin, k, seed):
 
 def _unpack(wp, wu, cout, cin, k):
     """The pack back to [Cout, Cin, k, k] float64 (hi + lo, unscaled), straight from the documented layout."""
-    p = wp.view(torch.float16).double().view(k * k, cin // 32, 2, cout, 32)
-    w = (p[:, :, 0] + p[:, :, 1]) * wu.double().view(1, 1, cout, 1)           # [tap][cb][co][kk]
-    return w.permute(2, 1, 3, 0).reshape(cout, cin, k, k)
+    return conv_ref.unpack_conv_weights(wp, wu, cout, cin, k)
 
 
 @pytest.mark.parametrize('k', [1, 3])

@@ -14,6 +14,8 @@ import torch.nn.functional as F
 
 from conftest import ROOT
 
+import conv_ref
+
 SRC = os.path.join(ROOT, 'rmnet_amd', 'csrc', 'stem.hip')
 
 
@@ -33,11 +35,7 @@ def _weights(cout, cin, k, seed):
 
 def _unpack(wp, wu, cin):
     """The stem pack back to ([64, Cin, 7, 7] float64 (hi + lo, unscaled), the K padding's planes), from the documented layout."""
-    kp = (49 * cin + 31) // 32 * 32
-    p = wp.view(torch.float16).double().view(kp // 32, 2, 64, 32)
-    flat = (p[:, 0] + p[:, 1]).permute(1, 0, 2).reshape(64, kp) * wu.double().view(64, 1)        # [co][k]
-    pad = p.permute(2, 1, 0, 3).reshape(64, 2, kp)[:, :, 49 * cin:]
-    return flat[:, :49 * cin].reshape(64, 7, 7, cin).permute(0, 3, 1, 2), pad
+    return conv_ref.unpack_stem_weights(wp, wu, cin)
 
 
 @pytest.mark.parametrize('cin', [3, 5])
