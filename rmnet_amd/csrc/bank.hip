@@ -75,6 +75,14 @@ __device__ inline void split_f16(float x, _Float16& hi, _Float16& lo) {
   hi = (_Float16)c;
   lo = (_Float16)fminf(fmaxf(x - (float)hi, -65504.0f), 65504.0f);
 }
+// A product ROUNDED to fp32, whatever follows.  The query is scaled once in fp32 and then split; written as `q * qscale` hipcc
+// contracts the product into split_f16's `x - hi` (one v_fma_mix: -ffp-contract=fast) and the lo plane then holds the product's
+// rounding residual -- an arithmetic that differs between the modes and that no host can restate (__fmul_rn is contracted all the
+// same; profiles/r11_a_bank_exact_tests.md).
+__device__ inline float mul_rounded(float a, float b) {
+#pragma clang fp contract(off)
+  return a * b;
+}
 // Keys and values are stored times 2^kBankShift (exact): fp16's window then covers |x| from
 // 65504 / 64 = 1023.5 down to an absolute error floor of 2^-25 / 64 = 4.7e-10 per element (the lo
 // plane is subnormal below |x| = 2^-3 / 64), which is where conv-net activations live; 1/64 is folded
@@ -426,7 +434,7 @@ __device__ inline void producer_loop(const BArgs& a, const Walk& wk, char* Kl_, 
     for (int ks = 0; ks < 4; ++ks)
 #pragma unroll
       for (int e = 0; e < 8; ++e) {
-        const float x = qb[(size_t)(32 * ks + 8 * g + e) * b.hw] * keep;
+        const float x = mul_rounded(qb[(size_t)(32 * ks + 8 * g + e) * b.hw], keep);
         _Float16 hi, lo;
         split_f16(x, hi, lo);              // (saturates; an element outside the window is COUNTED by a consumer wave: query_range_check)
         qh[ks][e] = hi; ql[ks][e] = lo;
@@ -798,7 +806,7 @@ __device__ inline void producer_loop_pp(const BArgs& a, const Walk& wk, char* Kl
     for (int ks = 0; ks < 4; ++ks)
 #pragma unroll
       for (int e = 0; e < 8; ++e) {
-        const float x = qb[(size_t)(32 * ks + 8 * g + e) * b.hw] * keep;   // (range: query_range_check)
+        const float x = mul_rounded(qb[(size_t)(32 * ks + 8 * g + e) * b.hw], keep);   // (range: query_range_check)
         if constexpr (kQx) {
           _Float16 hi, lo;
           split_f16(x, hi, lo);
