@@ -24,8 +24,12 @@
 // Per K step (32 of K) and workgroup:
 //   global reads   activations 128 px x 32 ch x 4 B  = 16 KB   (fp32; split in registers)
 //                  weights     256 co x 32 x 2 planes x 2 B = 32 KB  (pre-split, pre-packed, L2-resident)
-//   LDS            one buffer  X hi/lo [128][32] + W hi/lo [256][32] fp16 = 48 KB, two buffers = 96 KB;
-//                  one barrier per step (store the next step's tile while the MFMAs read this one)
+//   LDS            one buffer  X hi/lo [128][32] + W hi/lo [256][32] fp16 = 48 KB, two buffers = 96 KB = 98304 B, which is also
+//                  what the kernel is allocated (tests/test_kernel_resources.py); one barrier per step (store the next step's
+//                  tile while the MFMAs read this one)
+//   LDS writes     48 KB: the next step's tile, nothing else.  The prefetched operands wait in VGPRs (2 x float4 of
+//                  activations, 4 x 16 B of weights per thread): their loads are issued before the step's first MFMA and
+//                  waited for after its last
 //   LDS reads      per wave 8 A + 8 B fragments x 1 KB = 16 KB, per CU 128 KB (~512 clk at 256 B/clk)
 //   MFMA           per wave 4 x 4 tiles x 3 terms = 48 x v_mfma_f32_16x16x32_f16 (16 clk) = 768 clk;
 //                  two waves per SIMD -> 1536 clk per step per SIMD, which is the bound.
@@ -40,6 +44,8 @@ namespace {
 typedef _Float16 half8 __attribute__((ext_vector_type(8)));
 typedef _Float16 half4 __attribute__((ext_vector_type(4)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));   // 16 bytes of packed weights.  A native vector: an array of HIP's
+                                                                    // uint4 (a struct) is not kept in registers but placed in LDS
 
 constexpr int kCout = 256;       // output channels (fixed)
 constexpr int kMT = 128;         // pixels per workgroup
@@ -90,7 +96,7 @@ __global__ __launch_bounds__(kThreads) void conv3x3_split(ConvArgs a) {
     pw[i] = r % a.W;
   }
   f32x4 xr[2];
-  uint4 wr[4];
+  u32x4 wr[4];
   int bad = 0;
 
   auto load = [&](int s) {
@@ -106,7 +112,7 @@ __global__ __launch_bounds__(kThreads) void conv3x3_split(ConvArgs a) {
         xr[i] = f32x4{0.f, 0.f, 0.f, 0.f};
       }
     }
-    const uint4* wsrc = reinterpret_cast<const uint4*>(a.wp) + (size_t)s * (2 * kWPlane / 8);
+    const u32x4* wsrc = reinterpret_cast<const u32x4*>(a.wp) + (size_t)s * (2 * kWPlane / 8);
 #pragma unroll
     for (int i = 0; i < 4; ++i) wr[i] = wsrc[tid + kThreads * i];
   };
@@ -139,7 +145,7 @@ __global__ __launch_bounds__(kThreads) void conv3x3_split(ConvArgs a) {
     for (int i = 0; i < 4; ++i) {
       const int q = tid + kThreads * i;
       const int plane = q >> 10, co = (q >> 2) & (kCout - 1), ch = q & 3;
-      *reinterpret_cast<uint4*>(wb + plane * kWPlane + swz(co, ch)) = wr[i];
+      *reinterpret_cast<u32x4*>(wb + plane * kWPlane + swz(co, ch)) = wr[i];
     }
   };
 
@@ -155,9 +161,7 @@ __global__ __launch_bounds__(kThreads) void conv3x3_split(ConvArgs a) {
   store(0, lds);
   __syncthreads();
   const int fr = lane & 15, fc = lane >> 4;
-  for (int s = 0; s < steps; ++s) {
-    _Float16* cur = lds + (s & 1) * kBufHalves;
-    if (s + 1 < steps) load(s + 1);
+  auto mma = [&](const _Float16* cur) {
     const _Float16* xh = cur;
     const _Float16* xl = cur + kXPlane;
     const _Float16* wh = cur + 2 * kXPlane;
@@ -181,24 +185,64 @@ __global__ __launch_bounds__(kThreads) void conv3x3_split(ConvArgs a) {
 #pragma unroll
       for (int i = 0; i < 4; ++i) accx[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(al, bh[i], accx[i][j], 0, 0, 0);
     }
-    if (s + 1 < steps) store(s + 1, lds + ((s + 1) & 1) * kBufHalves);
+  };
+  // Steps 0 .. steps-2 prefetch their successor; the last step is apart, so that the loop body has no branch around the loads
+  // and the stores: with one, the compiler cannot tell at the loop's head which loads are still in flight and waits for the
+  // activation loads before it issues the weight loads and the MFMAs.
+  for (int s = 0; s + 1 < steps; ++s) {
+    load(s + 1);
+    __builtin_amdgcn_sched_barrier(0);     // (all of the step's global loads are in flight before its first MFMA ...
+    mma(lds + (s & 1) * kBufHalves);
+    __builtin_amdgcn_sched_barrier(0);     //  ... and nothing that waits for them is moved in among the MFMAs)
+    store(s + 1, lds + ((s + 1) & 1) * kBufHalves);
     __syncthreads();
   }
+  mma(lds + ((steps - 1) & 1) * kBufHalves);
 
   // epilogue: D[co][px] -- lane holds pixel fr of each 16-pixel tile and the 4 consecutive channels 4*fc .. of each
-  // 16-channel tile, i.e. one float4 of NHWC memory per (tile pair)
+  // 16-channel tile, i.e. one float4 of NHWC memory per (tile pair).
+  // The residual: out may BE res, so the compiler keeps every read of res in front of the stores that follow it in the source.
+  // All 16 reads are therefore issued here, before the first store (one round trip, not 16 dependent ones; the loader's registers
+  // are dead by now).  This is safe with out == res: a thread reads exactly the elements it later writes, and no other thread
+  // touches them.
+  f32x4 r[4][4];
+  if (a.res) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int m = m0 + wm * 64 + i * 16 + fr;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int co = wn * 64 + j * 16 + 4 * fc;
+        r[i][j] = m < a.M ? *reinterpret_cast<const f32x4*>(a.res + (size_t)m * kCout + co) : f32x4{0.f, 0.f, 0.f, 0.f};
+      }
+    }
+  }
+  // Unscale and shift in place, for all tiles, before the first store: for all the compiler knows these vectors alias out too, and
+  // read between the stores they would cost one more waited-for round trip per channel tile.
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
     const int co = wn * 64 + j * 16 + 4 * fc;
     const f32x4 us = *reinterpret_cast<const f32x4*>(a.w_unscale + co) * kActUnscale;
     const f32x4 b = a.bias ? *reinterpret_cast<const f32x4*>(a.bias + co) : f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
+    for (int i = 0; i < 4; ++i) acc[i][j] = (acc[i][j] + accx[i][j]) * us + b;
+  }
+  // (An empty statement the optimiser cannot see through: without it the loop above is sunk into the guarded stores below, and
+  // each tile's wait for its unscale vector then includes the stores issued before it.)
+#pragma unroll
+  for (int j = 0; j < 4; ++j)
+#pragma unroll
+    for (int i = 0; i < 4; ++i) asm volatile("" : "+v"(acc[i][j]));
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const int co = wn * 64 + j * 16 + 4 * fc;
+#pragma unroll
     for (int i = 0; i < 4; ++i) {
       const int m = m0 + wm * 64 + i * 16 + fr;
       if (m >= a.M) continue;
       const size_t off = (size_t)m * kCout + co;
-      f32x4 v = (acc[i][j] + accx[i][j]) * us + b;
-      if (a.res) v += *reinterpret_cast<const f32x4*>(a.res + off);
+      f32x4 v = acc[i][j];
+      if (a.res) v += r[i][j];
       if (a.relu_out) {
 #pragma unroll
         for (int e = 0; e < 4; ++e) v[e] = v[e] < 0.0f ? 0.0f : v[e];
@@ -224,7 +268,9 @@ extern "C" int rmnet_conv3x3_split_f32(const float* x, const void* wpack, const 
   if (Cin % kKT) return RMNET_E_UNSUPPORTED;
   const long long M = (long long)N * H * W;
   if (M * (long long)(Cin > kCout ? Cin : kCout) >= (1LL << 31)) return RMNET_E_UNSUPPORTED;   // (int pixel index, size_t offsets)
-  // out must not overlap x (other workgroups read x's halo); it may BE res (each element is read, then written, by one thread)
+  // out must not overlap x (other workgroups read x's halo); it may BE res: each element is read, then written, by one thread.  The
+  // epilogue reads all of a thread's residual values before its first store; a thread reads exactly the elements it later writes
+  // and no other thread touches them, so that is safe as well
   const char* xb = reinterpret_cast<const char*>(x);
   const char* ob = reinterpret_cast<const char*>(out);
   if (ob < xb + M * Cin * sizeof(float) && xb < ob + M * kCout * sizeof(float)) return RMNET_E_INVALID_ARG;

@@ -14,13 +14,15 @@
 // picks the NT-channel slice of Cout.  Waves are WM (pixels) x WN (channels), each owns TI x TJ 16x16 MFMA tiles.  Tiles
 // (chosen on the host, rmnet_conv_split_f32):
 //   Big    MT 128 x NT 256 (WM 2, WN 4, 4x4 tiles/wave)  Cout % 256 == 0 on maps that give >= 512 workgroups: the
-//          decoder kernel's shape (216 VGPRs, 96 KB of LDS -- 128 KB as allocated: one workgroup per CU);
+//          decoder kernel's shape (238 VGPRs, 96 KB of LDS, declared and allocated: one workgroup per CU);
 //   Mid    MT 128 x NT 128 (WM 2, WN 4, 4x2 tiles/wave)  Cout % 128 == 0 otherwise: the 1/16 maps (M = 25,920 at the
-//          bench shape) give only 203 Big workgroups for 256 CUs.  Held to 128 VGPRs (4 waves per SIMD) and 80 KB of
+//          bench shape) give only 203 Big workgroups for 256 CUs.  Held to 128 VGPRs (4 waves per SIMD) and 64 KB of
 //          LDS, two Mid workgroups share a CU, so the 406 of a 256-channel 1/16 convolution run in one round;
 //   Narrow MT 128 x NT 64  (WM 4, WN 2, 2x2 tiles/wave)  Cout = 64 (layer1 at 1/4), also two workgroups per CU.
-// Every tile's register budget is checked with -Rpass-analysis=kernel-resource-usage: no spills.
-// One LDS double buffer (X hi/lo [MT][32] + W hi/lo [NT][32] fp16), one barrier per K step, as in conv3x3.hip.
+// Every tile's registers, LDS and scratch are asserted from the compiler's metadata by tests/test_kernel_resources.py: no spills,
+// and exactly the declared LDS (96 / 64 / 48 KB).
+// One LDS double buffer (X hi/lo [MT][32] + W hi/lo [NT][32] fp16), one barrier per K step, as in conv3x3.hip.  The next step's
+// operands are prefetched into VGPRs (native vector types: an array of HIP's uint4 would be placed in LDS) while the MFMAs run.
 #include "common.h"
 
 namespace rmnet {
@@ -29,6 +31,7 @@ namespace {
 typedef _Float16 half8 __attribute__((ext_vector_type(8)));
 typedef _Float16 half4 __attribute__((ext_vector_type(4)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));   // 16 bytes of packed weights (native vector: see conv3x3.hip)
 
 constexpr int kKT = 32;          // K per step (one tap x 32 input channels)
 constexpr int kThreads = 512;
@@ -41,7 +44,7 @@ __device__ inline int swz(int row, int chunk) { return row * kKT + ((chunk ^ ((r
 
 struct SplitArgs {
   const float* x;          // [N][H][W][Cin]
-  const uint4* wp;         // [k*k][Cin / 32][2][Cout][32] fp16
+  const u32x4* wp;         // [k*k][Cin / 32][2][Cout][32] fp16
   const float* unscale;    // [Cout]
   const float* shift;      // [Cout] or null
   const float* res;        // [M][Cout] or null
@@ -82,10 +85,10 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(WPE)))
     pbase[i] = (n * a.H + ph[i]) * a.W + pw[i];
   }
   f32x4 xr[XI];
-  uint4 wr[WI];
+  u32x4 wr[WI];
   int bad = 0;
 
-  auto load = [&](int s) {
+  auto load_x = [&](int s) {
     const int tap = s / CB, cb = s - tap * CB;
     const int ky = tap / a.ksize, kx = tap - ky * a.ksize;
 #pragma unroll
@@ -98,7 +101,9 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(WPE)))
         xr[i] = f32x4{0.f, 0.f, 0.f, 0.f};
       }
     }
-    const uint4* wsrc = a.wp + (size_t)s * (a.Cout * 8);
+  };
+  auto load_w = [&](int s) {
+    const u32x4* wsrc = a.wp + (size_t)s * (a.Cout * 8);
 #pragma unroll
     for (int i = 0; i < WI; ++i) {
       const int q = tid + kThreads * i;
@@ -109,12 +114,11 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(WPE)))
 
   auto counted = [&](int t) { return t == a.pad || (a.stride == 2 && a.ksize == 3 && t == 2); };
 
-  auto store = [&](int s, _Float16* buf) {
+  auto store_x = [&](int s, _Float16* buf) {
     const int tap = s / CB, ky = tap / a.ksize, kx = tap - ky * a.ksize;
     const bool count = blockIdx.y == 0 && counted(ky) && counted(kx);   // (every Cout slice reads the same inputs: count in one)
     _Float16* xh = buf;
     _Float16* xl = buf + kXPlane;
-    _Float16* wb = buf + 2 * kXPlane;
 #pragma unroll
     for (int i = 0; i < XI; ++i) {
       half4 hi, lo;
@@ -134,11 +138,14 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(WPE)))
       *reinterpret_cast<half4*>(xh + o) = hi;
       *reinterpret_cast<half4*>(xl + o) = lo;
     }
+  };
+  auto store_w = [&](_Float16* buf) {
+    _Float16* wb = buf + 2 * kXPlane;
 #pragma unroll
     for (int i = 0; i < WI; ++i) {
       const int q = tid + kThreads * i;
       const int plane = q / (NT * 4), co = (q >> 2) % NT, ch = q & 3;
-      *reinterpret_cast<uint4*>(wb + plane * kWPlane + swz(co, ch)) = wr[i];
+      *reinterpret_cast<u32x4*>(wb + plane * kWPlane + swz(co, ch)) = wr[i];
     }
   };
 
@@ -148,13 +155,13 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(WPE)))
 #pragma unroll
     for (int j = 0; j < TJ; ++j) acc[i][j] = accx[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-  load(0);
-  store(0, lds);
+  load_x(0);
+  load_w(0);
+  store_x(0, lds);
+  store_w(lds);
   __syncthreads();
   const int fr = lane & 15, fc = lane >> 4;
-  for (int s = 0; s < steps; ++s) {
-    _Float16* cur = lds + (s & 1) * kBufHalves;
-    if (s + 1 < steps) load(s + 1);
+  auto mma = [&](const _Float16* cur, auto&& halfway) {
     const _Float16* xh = cur;
     const _Float16* xl = cur + kXPlane;
     const _Float16* wh = cur + 2 * kXPlane;
@@ -178,6 +185,7 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(WPE)))
         for (int i = 0; i < TI; ++i) accx[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bl[i], accx[i][j], 0, 0, 0);
 #pragma unroll
         for (int i = 0; i < TI; ++i) accx[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(al, bh[i], accx[i][j], 0, 0, 0);
+        if (j == TJ / 2 - 1) halfway();
       }
     } else {                              // the other way round (Mid, Narrow): 24 fragment VGPRs instead of 40, inside 128
       half8 ah[TJ], al[TJ];
@@ -198,25 +206,79 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(WPE)))
         for (int j = 0; j < TJ; ++j) accx[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[j], bl, accx[i][j], 0, 0, 0);
 #pragma unroll
         for (int j = 0; j < TJ; ++j) accx[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(al[j], bh, accx[i][j], 0, 0, 0);
+        if (i == TI / 2 - 1) halfway();
       }
     }
-    if (s + 1 < steps) store(s + 1, lds + ((s + 1) & 1) * kBufHalves);
+  };
+  // The last step is apart, so that the loop body has no branch around the loads and the stores (see conv3x3.hip).  Big and
+  // Narrow: all of a step's global loads are in flight before its first MFMA, and nothing that waits for them is moved in among
+  // the MFMAs.  Mid cannot hold 8 VGPRs of activations and 8 of weights in flight next to its fragments inside 128 VGPRs, so it
+  // takes them in turn: the activations fly during the first half of the MFMAs and are split and stored half way (the other
+  // buffer is free from the last barrier on), the weights fly during the second half.
+  constexpr bool kInTurn = TI > TJ && WPE == 4 && WI > 1;
+  for (int s = 0; s + 1 < steps; ++s) {
+    _Float16* nxt = lds + ((s + 1) & 1) * kBufHalves;
+    load_x(s + 1);
+    if constexpr (!kInTurn) load_w(s + 1);
+    __builtin_amdgcn_sched_barrier(0);
+    mma(lds + (s & 1) * kBufHalves, [&] {
+      if constexpr (kInTurn) {
+        __builtin_amdgcn_sched_barrier(0);
+        load_w(s + 1);
+        store_x(s + 1, nxt);
+        __builtin_amdgcn_sched_barrier(0);
+      }
+    });
+    __builtin_amdgcn_sched_barrier(0);
+    if constexpr (!kInTurn) store_x(s + 1, nxt);
+    store_w(nxt);
     __syncthreads();
   }
+  mma(lds + ((steps - 1) & 1) * kBufHalves, [] {});
 
-  // epilogue: D[co][px] -- lane holds pixel fr of each 16-pixel tile and channels 4*fc .. 4*fc+3 of each 16-channel tile
+  // epilogue: D[co][px] -- lane holds pixel fr of each 16-pixel tile and channels 4*fc .. 4*fc+3 of each 16-channel tile.
+  // The residual: out may BE res, so the compiler keeps every read of res in front of the stores that follow it in the source.
+  // All TI x TJ reads are therefore issued here, before the first store (one round trip, not TI x TJ dependent ones; the loader's
+  // registers are dead by now).  This is safe with out == res: a thread reads exactly the elements it later writes, and no other
+  // thread touches them.
+  f32x4 r[TI][TJ];
+  if (a.res) {
+#pragma unroll
+    for (int i = 0; i < TI; ++i) {
+      const int m = m0 + wm * TI * 16 + i * 16 + fr;
+#pragma unroll
+      for (int j = 0; j < TJ; ++j) {
+        const int co = n0 + wn * TJ * 16 + j * 16 + 4 * fc;
+        r[i][j] = m < a.M ? *reinterpret_cast<const f32x4*>(a.res + (size_t)m * a.Cout + co) : f32x4{0.f, 0.f, 0.f, 0.f};
+      }
+    }
+  }
+  // Unscale and shift in place, for all tiles, before the first store: for all the compiler knows these vectors alias out too, and
+  // read between the stores they would cost one more waited-for round trip per channel tile.
 #pragma unroll
   for (int j = 0; j < TJ; ++j) {
     const int co = n0 + wn * TJ * 16 + j * 16 + 4 * fc;
     const f32x4 us = *reinterpret_cast<const f32x4*>(a.unscale + co) * kActUnscale;
     const f32x4 b = a.shift ? *reinterpret_cast<const f32x4*>(a.shift + co) : f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
+    for (int i = 0; i < TI; ++i) acc[i][j] = (acc[i][j] + accx[i][j]) * us + b;
+  }
+  // (An empty statement the optimiser cannot see through: without it the loop above is sunk into the guarded stores below, and
+  // each tile's wait for its unscale vector then includes the stores issued before it.)
+#pragma unroll
+  for (int j = 0; j < TJ; ++j)
+#pragma unroll
+    for (int i = 0; i < TI; ++i) asm volatile("" : "+v"(acc[i][j]));
+#pragma unroll
+  for (int j = 0; j < TJ; ++j) {
+    const int co = n0 + wn * TJ * 16 + j * 16 + 4 * fc;
+#pragma unroll
     for (int i = 0; i < TI; ++i) {
       const int m = m0 + wm * TI * 16 + i * 16 + fr;
       if (m >= a.M) continue;
       const size_t off = (size_t)m * a.Cout + co;
-      f32x4 v = (acc[i][j] + accx[i][j]) * us + b;
-      if (a.res) v += *reinterpret_cast<const f32x4*>(a.res + off);
+      f32x4 v = acc[i][j];
+      if (a.res) v += r[i][j];
       if (a.relu_out) {
 #pragma unroll
         for (int e = 0; e < 4; ++e) v[e] = v[e] < 0.0f ? 0.0f : v[e];
@@ -259,8 +321,9 @@ extern "C" int rmnet_conv_split_f32(const float* x, const void* wpack, const flo
   const int Ho = (H + 2 * pad - ksize) / stride + 1, Wo = (W + 2 * pad - ksize) / stride + 1;
   const long long Mi = (long long)N * H * W, M = (long long)N * Ho * Wo;
   if (Mi * Cin >= (1LL << 31) || M * Cout >= (1LL << 31)) return RMNET_E_UNSUPPORTED;   // (int pixel index, size_t offsets)
-  // out must not overlap x (other workgroups read the same input pixels); it may BE res (each element is read, then written, by
-  // one thread)
+  // out must not overlap x (other workgroups read the same input pixels); it may BE res: each element is read, then written, by
+  // one thread.  The epilogue reads all of a thread's residual values before its first store; a thread reads exactly the elements
+  // it later writes and no other thread touches them, so that is safe as well
   const char* xb = reinterpret_cast<const char*>(x);
   const char* ob = reinterpret_cast<const char*>(out);
   const long long c1 = out2 ? out_split : Cout;
@@ -271,7 +334,7 @@ extern "C" int rmnet_conv_split_f32(const float* x, const void* wpack, const flo
     if (o2 < ob + M * c1 * sizeof(float) && ob < o2 + M * (Cout - c1) * sizeof(float)) return RMNET_E_INVALID_ARG;
   }
   SplitArgs a;
-  a.x = x; a.wp = reinterpret_cast<const uint4*>(wpack); a.unscale = w_unscale; a.shift = shift; a.res = res; a.out = out; a.out2 = out2;
+  a.x = x; a.wp = reinterpret_cast<const u32x4*>(wpack); a.unscale = w_unscale; a.shift = shift; a.res = res; a.out = out; a.out2 = out2;
   a.range = range_word; a.M = (int)M; a.H = H; a.W = W; a.Ho = Ho; a.Wo = Wo; a.Cin = Cin; a.Cout = Cout; a.csplit = (int)c1;
   a.ksize = ksize; a.stride = stride; a.pad = pad;
   a.relu_in = (flags & RMNET_CONV_RELU_IN) != 0;
