@@ -343,6 +343,36 @@ int rmnet_stem_split_f32(const float *frame, const float *mask, const float *oth
  * No window and no range word.  RMNET_E_UNSUPPORTED for C % 32 != 0 or n*Hq*Wq*C >= 2^31. */
 int rmnet_pred_head_f32(const float *x, const float *w, const float *bias, int n, int Hq, int Wq, int C, float *out, void *stream);
 
+/* C2 TinyFlowNet's wide convolutions (additive export, same ABI version): the arithmetic and range word of rmnet_conv_split_f32 over a
+ * tap list (csrc/flow_conv.hip), for forward convolutions with ksize = 3 or 5 (padding ksize / 2), stride 1 or 2, and -- with
+ * RMNET_FLOW_TRANSPOSED -- for ConvTranspose2d(4, stride 2, padding 1) (ksize 4, stride 2) as four 2x2-tap phases, one per output
+ * parity.  Input and output carry a channel stride, so that a layer reads and writes concatenation buffers in place.  Replaces
+ * conv2 .. conv5_1 and deconv4 .. deconv2 of TinyFlowNet (models/tiny_flownet.py) with their bias + LeakyReLU(0.1) and the torch.cat
+ * of their outputs.
+ *   x     [N, H, W, x_ld] fp32: channels 0 .. Cin-1 of every pixel are the input; x_ld % 4 == 0, x_ld >= ceil32(Cin) (Cin rounded up
+ *         to a multiple of 32).  Channels Cin .. ceil32(Cin)-1 are read and multiplied by the pack's zero weights: any bit pattern;
+ *   out   [N, Ho, Wo, out_ld] fp32: channels coff .. coff+Cout-1 of every pixel = act(conv(x) + shift[co]); no other byte is
+ *         written.  out_ld % 4 == 0, coff % 4 == 0, coff + Cout <= out_ld.  Ho = (H + 2 * pad - ksize) / stride + 1, or 2 * H
+ *         transposed (Wo alike).  act: none, ReLU (RMNET_FLOW_RELU) or y > 0 ? y : y * 0.1f (RMNET_FLOW_LEAKY); not both.
+ *         shift [Cout] may be NULL.  The byte ranges of x and out (whole strided buffers) must not overlap;
+ *   range_word: device int32, may be NULL.  Elements of the channels 0 .. Cin-1 with |x| >= 1023.5, NaN or Inf are saturated and
+ *         counted, once per tap that reads them (so possibly several times): zero means no such element was read.
+ * x, wpack, w_unscale, shift, out 16-byte aligned.  RMNET_E_UNSUPPORTED for another ksize / stride, Cout % 64 != 0, or
+ * N*H*W*x_ld or N*Ho*Wo*out_ld >= 2^31; RMNET_E_INVALID_ARG for everything else.
+ *
+ * Weight pack (rmnet_amd.ops.flow_conv_pack), Cp = ceil32(Cin), e / ws / hi / lo / w_unscale as for rmnet_conv_split_f32:
+ *   forward     w [Cout][Cin][k][k]:  fp16 [k*k][Cp / 32][2][Cout][32]: [tap = k * ky + kx][ci / 32][plane: hi, lo][co][ci % 32];
+ *   transposed  w [Cin][Cout][4][4]:  fp16 [4][4][Cp / 32][2][Cout][32]: [phase = 2 * a + b][tap = 2 * ty + tx][ci / 32][plane][co][ci % 32]
+ *               holding w[ci][co][3 - a - 2 * ty][3 - b - 2 * tx]; phase (a, b) computes the output pixels (2 i + a, 2 j + b) from the
+ *               input pixels (i + a - 1 + ty, j + b - 1 + tx);
+ *   both zero for ci >= Cin. */
+#define RMNET_FLOW_RELU 1
+#define RMNET_FLOW_LEAKY 2
+#define RMNET_FLOW_TRANSPOSED 4
+int rmnet_flow_conv_f32(const float *x, int x_ld, const void *wpack, const float *w_unscale, const float *shift, int flags, int N, int H,
+                        int W, int Cin, int Cout, int ksize, int stride, float *out, int out_ld, int coff, int32_t *range_word,
+                        void *stream);
+
 /* P3/P4 tail: decoder logits -> foreground probability -> soft aggregation -> un-pad (-> soft-max over
  * the K mask channels) in one pass.  dec [n_tot,2,Hp,Wp]: 2-class logits of the objects in flight;
  * clip b owns objects [obj_begin[b], obj_begin[b+1]) (device int32 [B+1]); logit / prob [B,K,H,W] with

@@ -709,6 +709,129 @@ def conv_split(x, wpack, w_unscale, shift=None, res=None, ksize=3, stride=1, rel
     return out if out2 is None else (out, out2)
 
 
+FLOW_RELU, FLOW_LEAKY, FLOW_TRANSPOSED = 1, 2, 4   # RMNET_FLOW_*
+_FLOW_ACT = {None: 0, False: 0, 'none': 0, True: FLOW_RELU, 'relu': FLOW_RELU, 'leaky': FLOW_LEAKY}
+
+
+def flow_conv_phase_weights(weight):
+    """ConvTranspose2d(4, stride 2, padding 1) weight [Cin, Cout, 4, 4] -> [4, Cout, Cin, 2, 2]: the four 2x2-tap forward kernels of
+    the output parities.  Phase 2a + b computes the output pixels (2i + a, 2j + b) from the input pixels (i + a - 1 + ty,
+    j + b - 1 + tx), ty, tx in {0, 1}, with the weight of ky = 3 - a - 2 ty, kx = 3 - b - 2 tx (from y = 2 iy - 1 + ky)."""
+    w = weight.permute(1, 0, 2, 3)
+    phases = []
+    for a in (0, 1):
+        for b in (0, 1):
+            ky = torch.tensor([3 - a, 1 - a], device=w.device)
+            kx = torch.tensor([3 - b, 1 - b], device=w.device)
+            phases.append(w.index_select(2, ky).index_select(3, kx))
+    return torch.stack(phases, 0)
+
+
+@torch.no_grad()
+def flow_conv_pack(weight, transposed=False):
+    """fp32 weight -> (wpack fp16 bits as int16, w_unscale fp32 [Cout]) in the layout of include/rmnet_hip.h (rmnet_flow_conv_f32):
+    ``conv_split_pack``'s scheme -- per output channel a power-of-two scale 2^e puts max |w| in [2^14, 2^15), hi = rne(ws),
+    lo = rne(ws - hi), [tap][Cin_p / 32][hi, lo][co][32] -- with the input channels zero-padded to Cin_p = ceil32(Cin).
+    ``transposed=False``: a [Cout, Cin, k, k] Conv2d weight, k = 3 or 5, one pack.  ``transposed=True``: a [Cin, Cout, 4, 4]
+    ConvTranspose2d(4, stride 2, padding 1) weight, rearranged into the four 2x2-tap phase packs (``flow_conv_phase_weights``), one
+    after the other, under one scale per output channel.  Cout % 64 == 0."""
+    if weight.dim() != 4 or weight.shape[2] != weight.shape[3] or weight.shape[2] not in ((4,) if transposed else (3, 5)):
+        raise RuntimeError('flow_conv_pack needs a [Cout, Cin, k, k] weight with k in (3, 5), or transposed a [Cin, Cout, 4, 4] one, '
+                           'got %s' % (tuple(weight.shape),))
+    if weight.dtype != torch.float32:
+        raise RuntimeError('flow_conv_pack needs fp32 weights, got %s' % weight.dtype)
+    w = weight.detach().double()
+    w = flow_conv_phase_weights(w) if transposed else w.unsqueeze(0)          # [P, Cout, Cin, KH, KW]
+    P, cout, cin, kh, kw = w.shape
+    if cout % 64:
+        raise RuntimeError('flow_conv_pack needs Cout % 64 == 0, got ' + str(cout))
+    cp = (cin + 31) // 32 * 32
+    amax = w.abs().amax(dim=(0, 2, 3, 4))
+    _, ex = torch.frexp(amax)                              # amax in [2^(ex-1), 2^ex)
+    e = torch.where(amax > 0, 15 - ex, torch.zeros_like(ex))
+    ws = torch.ldexp(w, e.view(1, -1, 1, 1, 1).to(w.dtype))   # exact: power-of-two scaling
+    hi = ws.half()
+    lo = (ws - hi.double()).half()
+    pad = lambda p: torch.nn.functional.pad(p, (0, 0, 0, 0, 0, cp - cin))
+    planes = torch.stack([pad(p).reshape(P, cout, cp // 32, 32, kh * kw).permute(0, 4, 2, 1, 3) for p in (hi, lo)], dim=3)
+    unscale = torch.ldexp(torch.ones_like(amax), (-e).to(amax.dtype)).float()
+    return planes.contiguous().view(-1).view(torch.int16), unscale.contiguous()
+
+
+def flow_conv_out_hw(H, W, ksize, stride, transposed):
+    if transposed:
+        return 2 * H, 2 * W
+    pad = ksize // 2
+    return (H + 2 * pad - ksize) // stride + 1, (W + 2 * pad - ksize) // stride + 1
+
+
+def flow_conv(x, wpack, w_unscale, shift=None, *, ksize=3, stride=1, transposed=False, act=None, cin=None, out=None, out_coff=0,
+              range_word=None):
+    """act(conv(x[:, :cin], w) + shift) on the split-fp16 tap-list kernel (csrc/flow_conv.hip): a forward convolution with ``ksize``
+    3 or 5 (padding ksize // 2) and ``stride`` 1 or 2, or, ``transposed``, ConvTranspose2d(4, stride 2, padding 1) (``ksize=4,
+    stride=2``).  ``wpack, w_unscale`` come from ``flow_conv_pack``; Cout = ``w_unscale.numel()``.  ``act``: None, 'relu' or
+    'leaky' (LeakyReLU(0.1), the expression of ``channel_affine``).
+    ``x`` is a channels-last fp32 [N, x_ld, H, W] tensor of which the first ``cin`` channels (default: all) are the input: a
+    channel-padded buffer, x_ld % 4 == 0 and x_ld >= ceil32(cin); what the channels cin .. ceil32(cin) - 1 hold does not matter.
+    ``out``: None for a new channels-last [N, Cout, Ho, Wo] tensor, or a channels-last [N, out_ld, Ho, Wo] buffer of which only the
+    channels ``out_coff .. out_coff + Cout - 1`` are written (both multiples of 4); it must not share memory with ``x``.  Returns
+    ``out``.  ``range_word`` (int32 [1]): as for ``conv3x3_split``, but an element may be counted more than once.  No fall-back:
+    anything else is a RuntimeError."""
+    _check_act(x, 'x')
+    if x.dim() != 4 or not x.is_contiguous(memory_format=torch.channels_last):
+        raise RuntimeError('x must be a channels-last [N, C, H, W] tensor')
+    if transposed:
+        if ksize != 4 or stride != 2:
+            raise RuntimeError('flow_conv implements the transposed convolution for ksize 4 / stride 2, got %r / %r' % (ksize, stride))
+    elif ksize not in (3, 5) or stride not in (1, 2):
+        raise RuntimeError('flow_conv implements ksize 3 / 5 and stride 1 / 2, got %r / %r' % (ksize, stride))
+    if act not in _FLOW_ACT:
+        raise RuntimeError("act must be None, 'relu' or 'leaky', got %r" % (act,))
+    N, x_ld, H, W = x.shape
+    cin = x_ld if cin is None else int(cin)
+    cp = (cin + 31) // 32 * 32
+    if cin <= 0 or x_ld % 4 or x_ld < cp:
+        raise RuntimeError('flow_conv needs x_ld %% 4 == 0 and x_ld >= ceil32(cin): x has %d channels for cin = %d' % (x_ld, cin))
+    _check(w_unscale, 'w_unscale')
+    cout = w_unscale.numel()
+    if cout % 64 or cout == 0:
+        raise RuntimeError('flow_conv needs Cout % 64 == 0, got ' + str(cout))
+    _check(wpack, 'wpack', torch.int16)
+    want = (16 if transposed else ksize * ksize) * cp * cout * 2
+    if wpack.numel() != want:
+        raise RuntimeError('wpack has %d elements, a %dx%d%s cin = %d Cout = %d pack has %d'
+                           % (wpack.numel(), ksize, ksize, ' transposed' if transposed else '', cin, cout, want))
+    if shift is not None:
+        _check(shift, 'shift')
+        if shift.numel() != cout:
+            raise RuntimeError('shift must have Cout = %d elements' % cout)
+    Ho, Wo = flow_conv_out_hw(H, W, ksize, stride, transposed)
+    if out is None:
+        if out_coff:
+            raise RuntimeError('out_coff without out')
+        out = torch.empty((N, cout, Ho, Wo), dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
+    else:
+        _check_act(out, 'out')
+        if out.dim() != 4 or not out.is_contiguous(memory_format=torch.channels_last) or \
+                (out.shape[0], out.shape[2], out.shape[3]) != (N, Ho, Wo):
+            raise RuntimeError('out must be a channels-last [%d, out_ld, %d, %d] tensor' % (N, Ho, Wo))
+        if out.shape[1] % 4 or out_coff % 4 or out_coff < 0 or out_coff + cout > out.shape[1]:
+            raise RuntimeError('flow_conv needs out_ld %% 4 == 0, out_coff %% 4 == 0 and out_coff + Cout <= out_ld, got %d, %d, %d'
+                               % (out.shape[1], out_coff, cout))
+    if range_word is not None:
+        _check(range_word, 'range_word', torch.int32)
+    for t in (wpack, w_unscale, shift, out, range_word):
+        if t is not None and t.device != x.device:
+            raise RuntimeError('flow_conv: every tensor must be on %s' % x.device)
+    flags = _FLOW_ACT[act] | (FLOW_TRANSPOSED if transposed else 0)
+    lib = _lib.load()
+    with torch.cuda.device(x.device):
+        rc = lib.rmnet_flow_conv_f32(_ptr(x), x_ld, _ptr(wpack), _ptr(w_unscale), _ptr(shift), flags, N, H, W, cin, cout, ksize, stride,
+                                     _ptr(out), out.shape[1], out_coff, _ptr(range_word), _stream(x.device))
+    _lib.check(rc, 'rmnet_flow_conv_f32')
+    return out
+
+
 STEM_COUT = 64                    # csrc/stem.hip: output channels of the encoder stems
 
 

@@ -1,5 +1,6 @@
 # -*- coding: utf-8 -*-
-"""TinyFlowNet on stock PyTorch-ROCm (SURVEY.md section 8 row C2 -- not re-implemented in HIP).
+"""TinyFlowNet on stock PyTorch-ROCm; on a fused channels-last network its ten wide convolutions run
+on a HIP kernel (csrc/flow_conv.hip, ``RMNET_FLOW_CONV``: see ``TinyFlowNet._forward``).
 
 Mirrors ``models/tiny_flownet.py`` of the reference: same constructor signature, same
 ``forward(frames) -> [B, N, 2, H, W]`` contract and the same state-dict keys
@@ -8,6 +9,8 @@ Mirrors ``models/tiny_flownet.py`` of the reference: same constructor signature,
 that the output buffer is allocated on the input's device (the reference allocates it on the
 host and copies every frame back, lines 121-132) -- values are identical.
 """
+
+import os
 
 import torch
 import torch.nn.functional as F
@@ -32,6 +35,25 @@ def _flow_head(c_in):
 
 def _flow_up():
     return nn.ConvTranspose2d(2, 2, 4, stride=2, padding=1, bias=False)
+
+
+# The default follows the bench line: three alternating runs per setting, every 'split' run above every 'miopen' run
+# (540.6 - 541.8 against 522.8 - 523.6 frames/s, profiles/r13_a_flow_conv.md).
+FLOW_CONV_DEFAULT = 'split'
+
+# The ten layers with 64 or more output channels (93 % of the network's FLOPs)
+FLOW_SPLIT_LAYERS = ('conv2', 'conv3', 'conv3_1', 'conv4', 'conv4_1', 'conv5', 'conv5_1', 'deconv4', 'deconv3', 'deconv2')
+# channels per pixel of cat4 / cat3 / cat2: 770 / 386 / 194 rounded up to a multiple of 32 (the kernel reads whole 32-channel steps)
+_CAT_LD = {4: 800, 3: 416, 2: 224}
+
+
+def flow_conv_backend():
+    """RMNET_FLOW_CONV (A/B switch, read at every call): 'split' (default) -- the ten wide convolutions of a fused, channels-last
+    TinyFlowNet run on the split-fp16 HIP kernel; 'miopen' -- none does."""
+    v = os.environ.get('RMNET_FLOW_CONV', FLOW_CONV_DEFAULT).lower()
+    if v not in ('split', 'miopen'):
+        raise RuntimeError('RMNET_FLOW_CONV must be split or miopen, got %r' % v)
+    return v
 
 
 class TinyFlowNet(nn.Module):
@@ -59,20 +81,32 @@ class TinyFlowNet(nn.Module):
 
     def _forward(self, img0, img1):
         """Flow for one frame pair (reference lines 84-119): pad to /64, halve, encode,
-        three refinement levels, x8 bilinear upsample, un-pad."""
+        three refinement levels, x8 bilinear upsample, un-pad.
+
+        After ``fuse_epilogues()``, in eval mode, on CUDA fp32 frames of a channels-last run (the frames or the weights channels-last)
+        and unless ``RMNET_FLOW_CONV=miopen``, the ten convolutions of ``FLOW_SPLIT_LAYERS`` run on the split-fp16 kernel
+        (csrc/flow_conv.hip) with bias + LeakyReLU in its epilogue, writing straight into the concatenation buffers.  That kernel
+        saturates activations outside |x| < 1023.5 and counts them in ``flow_range_word(device)``.  There is no host
+        synchronisation here (the call can be captured into a HIP graph): ``forward`` zeroes and checks the word once per clip, a
+        streaming caller of ``_forward`` checks ``flow_range_count()`` itself and, when it is non-zero, zeroes the word and redoes
+        the frames since its last check with ``RMNET_FLOW_CONV=miopen``."""
         (img0, img1), pad = pad_divide_by([img0, img1], 64, img0.shape[2:])
         pair = torch.cat((F.interpolate(img0, scale_factor=0.5, mode='bilinear'),
                           F.interpolate(img1, scale_factor=0.5, mode='bilinear')), dim=1)
         run = self._fused_block if getattr(self, '_fused', False) and not self.training and pair.is_cuda else (lambda m, x: m(x))
-        c2 = run(self.conv2, run(self.conv1, pair))
-        c3 = run(self.conv3_1, run(self.conv3, c2))
-        c4 = run(self.conv4_1, run(self.conv4, c3))
-        c5 = run(self.conv5_1, run(self.conv5, c4))
+        if self._flow_split_ok(pair):
+            flow2 = self._refine_split(run(self.conv1, pair))
+        else:
+            c2 = run(self.conv2, run(self.conv1, pair))
+            c3 = run(self.conv3_1, run(self.conv3, c2))
+            c4 = run(self.conv4_1, run(self.conv4, c3))
+            c5 = run(self.conv5_1, run(self.conv5, c4))
 
-        cat4 = torch.cat((c4, run(self.deconv4, c5), self.upsampled_flow5_to_4(self.predict_flow5(c5))), 1)
-        cat3 = torch.cat((c3, run(self.deconv3, cat4), self.upsampled_flow4_to_3(self.predict_flow4(cat4))), 1)
-        cat2 = torch.cat((c2, run(self.deconv2, cat3), self.upsampled_flow3_to_2(self.predict_flow3(cat3))), 1)
-        flow = F.interpolate(self.predict_flow2(cat2), scale_factor=8, mode='bilinear')
+            cat4 = torch.cat((c4, run(self.deconv4, c5), self.upsampled_flow5_to_4(self.predict_flow5(c5))), 1)
+            cat3 = torch.cat((c3, run(self.deconv3, cat4), self.upsampled_flow4_to_3(self.predict_flow4(cat4))), 1)
+            cat2 = torch.cat((c2, run(self.deconv2, cat3), self.upsampled_flow3_to_2(self.predict_flow3(cat3))), 1)
+            flow2 = self.predict_flow2(cat2)
+        flow = F.interpolate(flow2, scale_factor=8, mode='bilinear')
 
         lw, uw, lh, uh = pad
         if lh + uh > 0:
@@ -81,11 +115,120 @@ class TinyFlowNet(nn.Module):
             flow = flow[:, :, :, lw:flow.shape[3] - uw]
         return flow
 
+    # ------------------------------------------------------------------------------------------ the split-fp16 path
+    def _flow_split_ok(self, pair):
+        """The ten wide convolutions run on csrc/flow_conv.hip for this input: fused with packs on the input's device, eval, CUDA
+        fp32, a channels-last run, RMNET_FLOW_CONV not miopen, and not the MIOpen re-run of a clip that left the window."""
+        if not getattr(self, '_fused', False) or self.training or getattr(self, '_flow_off', False):
+            return False
+        packs = getattr(self, '_flow_packs', None)
+        if not packs or not (pair.is_cuda and pair.dtype == torch.float32 and packs['conv2'][0].device == pair.device):
+            return False
+        from .ops import _is_cl
+        if not (_is_cl(pair) or _is_cl(self.conv2[0].weight)):
+            return False
+        return flow_conv_backend() == 'split'
+
+    def _refine_split(self, c1):
+        """conv2 .. predict_flow2 on ``c1`` = conv1's output, the ten wide layers on the HIP kernel.  cat4 / cat3 / cat2 are ONE
+        channels-last buffer each (800 / 416 / 224 channels per pixel): conv4_1 / conv3_1 / conv2 write the channels from 0, the
+        deconvolutions theirs from 512 / 256 / 128, torch copies the two upsampled-flow channels behind them, and the padding up to
+        the next multiple of 32 is zeroed -- so no torch.cat is left.  The flow heads of the three buffers convolve the WHOLE buffer
+        with a zero-padded copy of their weight (``fuse_epilogues``): a channel-sliced view would be copied into a dense tensor
+        by the library first.  Every buffer is a fresh stream-ordered allocation: nothing is kept between calls, and nothing
+        depends on the frame, so the call can be captured."""
+        from . import ops
+        word = self.flow_range_word(c1.device)
+        self.__dict__['_flow_used'] = True            # (for ``forward``: a host flag, no synchronisation)
+
+        def fc(name, x, cin=None, out=None, coff=0):
+            conv = getattr(self, name)[0]
+            wp, wu = self._flow_packs[name]
+            tr = isinstance(conv, nn.ConvTranspose2d)
+            return ops.flow_conv(x, wp, wu, conv.bias, ksize=conv.kernel_size[0], stride=conv.stride[0], transposed=tr, act='leaky',
+                                 cin=cin, out=out, out_coff=coff, range_word=word)
+
+        def buf(level, src):          # the buffer of a level: half the map of the level above (k 5 / pad 2 and k 3 / pad 1, stride 2)
+            n, _, h, w = src.shape
+            return torch.empty((n, _CAT_LD[level], (h - 1) // 2 + 1, (w - 1) // 2 + 1), dtype=src.dtype, device=src.device,
+                               memory_format=torch.channels_last)
+
+        def tail(cat, real, up):
+            cat[:, real - 2:real].copy_(up)           # the upsampled flow, behind the deconvolution's channels
+            cat[:, real:].zero_()                     # the padding: finite for the kernel (zero weights), ZERO for the flow head
+
+        c1 = c1.contiguous(memory_format=torch.channels_last)      # (no copy in a channels-last run)
+        cat2 = buf(2, c1)
+        fc('conv2', c1, out=cat2)
+        cat3 = buf(3, cat2)
+        fc('conv3_1', fc('conv3', cat2, cin=128), out=cat3)
+        cat4 = buf(4, cat3)
+        fc('conv4_1', fc('conv4', cat3, cin=256), out=cat4)
+        c5 = fc('conv5_1', fc('conv5', cat4, cin=512))
+
+        fc('deconv4', c5, out=cat4, coff=512)
+        tail(cat4, 770, self.upsampled_flow5_to_4(self.predict_flow5(c5)))
+        fc('deconv3', cat4, cin=770, out=cat3, coff=256)
+        tail(cat3, 386, self.upsampled_flow4_to_3(self._flow_head(4, cat4)))
+        fc('deconv2', cat3, cin=386, out=cat2, coff=128)
+        tail(cat2, 194, self.upsampled_flow3_to_2(self._flow_head(3, cat3)))
+        return self._flow_head(2, cat2)
+
+    def _flow_head(self, level, cat):
+        head = getattr(self, 'predict_flow%d' % level)
+        return F.conv2d(cat, self._flow_head_w[level], head.bias, 1, 1)
+
+    def flow_range_word(self, device):
+        """This network's int32 range word on ``device`` (created on first use: ``fuse_epilogues`` does that for the weights'
+        device, outside any graph capture)."""
+        words = self.__dict__.setdefault('_flow_range', {})
+        idx = torch.device(device).index
+        idx = torch.cuda.current_device() if idx is None else idx
+        w = words.get(idx)
+        if w is None:
+            w = words[idx] = torch.zeros(1, dtype=torch.int32, device=torch.device('cuda', idx))
+        return w
+
+    def flow_range_count(self, device=None):
+        """How often the split-fp16 kernel met an activation outside its window since the word was last zeroed (host sync)."""
+        device = self.conv1[0].weight.device if device is None else device
+        return int(self.flow_range_word(device).item())
+
+    @torch.no_grad()
+    def _build_flow_packs(self):
+        """The ten weight packs, the zero-padded flow-head weights and the range word: plain attributes (not parameters or buffers,
+        so ``state_dict()`` is untouched), rebuilt whenever the parameters move (``_apply``) or are loaded."""
+        from . import ops
+        packs = {}
+        for name in FLOW_SPLIT_LAYERS:
+            conv = getattr(self, name)[0]
+            packs[name] = ops.flow_conv_pack(conv.weight.detach().float(), transposed=isinstance(conv, nn.ConvTranspose2d))
+        heads = {}
+        for level, ld in _CAT_LD.items():
+            w = getattr(self, 'predict_flow%d' % level).weight.detach()
+            heads[level] = F.pad(w, (0, 0, 0, 0, 0, ld - w.shape[1])).contiguous(memory_format=torch.channels_last)
+        self.__dict__['_flow_packs'] = packs
+        self.__dict__['_flow_head_w'] = heads
+        if self.conv1[0].weight.is_cuda:
+            self.flow_range_word(self.conv1[0].weight.device)
+
+    def _apply(self, fn, *args, **kwargs):
+        out = super()._apply(fn, *args, **kwargs)
+        if getattr(self, '_fused', False):
+            self._build_flow_packs()           # (the packs are no buffers: they follow the parameters this way)
+        return out
+
     def load_reference_state_dict(self, state_dict, strict=True):
         """Accepts the reference's checkpoints with or without DataParallel's ``module.`` prefix
         (core/inference.py:33-44)."""
         clean = {(k[7:] if k.startswith('module.') else k): v for k, v in state_dict.items()}
         return self.load_state_dict(clean, strict=strict)
+
+    def load_state_dict(self, *args, **kwargs):
+        out = super().load_state_dict(*args, **kwargs)
+        if getattr(self, '_fused', False):
+            self._build_flow_packs()
+        return out
 
     @staticmethod
     def _fused_block(block, x):
@@ -100,14 +243,39 @@ class TinyFlowNet(nn.Module):
         return ops.channel_affine(t, None, conv.bias, relu='leaky', out=t)
 
     def fuse_epilogues(self, enable=True):
-        """Bias + LeakyReLU of every block as one kernel (parameters untouched)."""
+        """Bias + LeakyReLU of every block as one kernel (parameters untouched), and the weight packs of the ten wide convolutions
+        for the split-fp16 kernel (plain attributes: ``state_dict()`` is unchanged; ``RMNET_FLOW_CONV=miopen`` leaves them unused)."""
         self.eval()
         self._fused = bool(enable)
+        if self._fused:
+            self._build_flow_packs()
+        else:
+            self.__dict__.pop('_flow_packs', None)
+            self.__dict__.pop('_flow_head_w', None)
         return self
 
     def forward(self, frames, device=None):
+        """Flow of every frame of a clip against its predecessor.  With the split-fp16 path on, the range word is zeroed before the
+        loop and read once after it; a clip that left the kernel's window is computed again with the kernel off.  ``last_clip`` says
+        which path the returned flows come from and what the word held."""
         # (the reference's DataParallel wrapper moves host frames to the GPU, core/inference.py:35-37)
         frames = frames.to(self.conv1[0].weight.device, non_blocking=True)
+        if frames.is_cuda:
+            self.flow_range_word(frames.device).zero_()
+        self.__dict__['_flow_used'] = False
+        flows = self._clip(frames)
+        split = self.__dict__['_flow_used']          # some frame pair took the split-fp16 path
+        count = self.flow_range_count(frames.device) if split else 0
+        if count:
+            self.__dict__['_flow_off'] = True
+            try:
+                flows = self._clip(frames)
+            finally:
+                self.__dict__['_flow_off'] = False
+        self.__dict__['last_clip'] = {'flow_conv': 'split' if split and not count else 'miopen', 'range': count}
+        return flows
+
+    def _clip(self, frames):
         b, n, _, h, w = frames.shape
         flows = frames.new_zeros(b, n, 2, h, w)
         for t in range(1, n):
