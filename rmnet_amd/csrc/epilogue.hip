@@ -151,7 +151,10 @@ __device__ inline float fg_prob(const float* __restrict__ dec, size_t plane, siz
   return e1 / (e0 + e1);
 }
 __device__ inline float em_logit(float em) {
-  em = fminf(fmaxf(em, 1e-7f), 1.0f - 1e-7f);
+  // comparisons, not fmaxf / fminf: those return the other operand for a NaN, which turned a NaN probability into the
+  // absent-channel logit; torch.clamp (models/rmnet.py:300) keeps it
+  em = em < 1e-7f ? 1e-7f : em;
+  em = em > 1.0f - 1e-7f ? 1.0f - 1e-7f : em;
   return logf(em / (1.0f - em));
 }
 

@@ -476,7 +476,11 @@ def channel_affine(x, scale=None, shift=None, res=None, res_scale=None, res_shif
 
 def upsample2x_add(x, skip=None, out=None):
     """skip + F.interpolate(x, scale_factor=2, mode='bilinear', align_corners=False) in one pass
-    (csrc/epilogue.hip); ``skip`` None = plain upsample; ``out`` may be ``skip`` (in place)."""
+    (csrc/epilogue.hip); ``skip`` None = plain upsample; ``out`` may be ``skip`` (in place).
+    The kernel is chosen by the operands: channels-last if ``x`` or ``skip`` is (the other one is converted), NCHW otherwise, and
+    the result has that memory format.  An NCHW ``out`` next to channels-last operands is NOT written: a new channels-last tensor
+    is returned instead (networks.Refine passes out=s whatever the layouts are and uses the returned value).  The other mismatch,
+    a channels-last ``out`` next to NCHW operands, raises: the NCHW kernel would fill its storage in the wrong order."""
     _check_act(x, 'x')
     if x.dim() != 4:
         raise RuntimeError('x must be [N,C,h,w]')
@@ -498,6 +502,8 @@ def upsample2x_add(x, skip=None, out=None):
         _check_act(out, 'out')
         if tuple(out.shape) != shape:
             raise RuntimeError('out must be [N,C,2h,2w]')
+        if not cl and not out.is_contiguous():
+            raise RuntimeError('out must have the memory format of x and skip (NCHW here, out is channels-last)')
     lib = _lib.load()
     with torch.cuda.device(x.device):
         if cl:
