@@ -28,12 +28,19 @@
 //                  what the kernel is allocated (tests/test_kernel_resources.py); one barrier per step (store the next step's
 //                  tile while the MFMAs read this one)
 //   LDS writes     48 KB: the next step's tile, nothing else.  The prefetched operands wait in VGPRs (2 x float4 of
-//                  activations, 4 x 16 B of weights per thread): their loads are issued before the step's first MFMA and
-//                  waited for after its last
+//                  activations, 4 x 16 B of weights per thread): all six loads are issued before the step's first MFMA; the
+//                  activations are waited for half way through the MFMAs, the weights after the last
 //   LDS reads      per wave 8 A + 8 B fragments x 1 KB = 16 KB, per CU 128 KB (~512 clk at 256 B/clk)
 //   MFMA           per wave 4 x 4 tiles x 3 terms = 48 x v_mfma_f32_16x16x32_f16 (16 clk) = 768 clk;
 //                  two waves per SIMD -> 1536 clk per step per SIMD, which is the bound.
-//   VALU split     8 elements per thread per step (~6 instructions each), negligible next to the MFMAs.
+//   VALU split     8 elements per thread per step, ~75 VALU instructions per wave with their addresses: 300 clk per wave, 600 per
+//                  SIMD, which is NOT negligible next to 1536 when it runs after the MFMAs (both waves of a SIMD share the one
+//                  barrier per step, so they split at the same time and the matrix pipe stands idle).  It is therefore issued
+//                  BETWEEN the MFMAs of the step's second half, one MFMA to three VALU instructions, and what it computes per
+//                  step is only what changes per step: the K loop runs over the taps and, inside a tap, over the channel blocks,
+//                  so the tap's offset and border test (a per-pixel 9-bit mask, a clamped address and a select of zero: no
+//                  branch) are set once per tap, and the input ReLU and the range count are compiled into the loop instance
+//                  that needs them (with / without ReLU x centre tap or not) instead of being tested per element.
 // Ceiling at the 1/4-resolution shape (M = 414720, Cin = 256): 3240 workgroups, 72 steps each,
 // 1536 clk/step -> ~13 rounds x 110 k clk / 2.4 GHz ~ 0.6 ms (= the 2.5 PF fp16 roof / 3).
 #include "common.h"
@@ -63,6 +70,11 @@ static_assert(2 * kBufHalves * 2 <= kLdsBytesPerCU, "LDS budget");
 // the fragment reads (16 rows x 4 chunks per 64 lanes) and the tile writes spread over all banks.
 __device__ inline int swz(int row, int chunk) { return row * kKT + ((chunk ^ ((row >> 1) & 3)) << 3); }
 
+template <bool B>
+struct Flag {
+  static constexpr bool value = B;
+};
+
 struct ConvArgs {
   const float* x;          // [M][Cin]
   const half8* wp;         // [9 * Cin / 32][2][256][32] fp16
@@ -79,58 +91,73 @@ __global__ __launch_bounds__(kThreads) void conv3x3_split(ConvArgs a) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wm = wave & 1, wn = wave >> 1;
   const int m0 = blockIdx.x * kMT;
-  const int HW = a.H * a.W, CB = a.Cin / kKT, steps = 9 * CB;
+  const int HW = a.H * a.W, CB = a.Cin / kKT;
 
   // loader items: activations 2 x float4 per thread (pixel p = tid/8 + 64i, channels 4*(tid&7) ..),
   // weights 4 x 16 B per thread (chunk q = tid + 512i of the step's 2048)
   const int c4 = tid & 7;
-  int ph[2], pw[2], pm[2];
-  bool pin[2];
+  int pm[2];               // the pixel (0 past M)
+  unsigned inside[2];      // bit t: tap t of this pixel lies inside the map (past M: none does) -- the border test, once per pixel
 #pragma unroll
   for (int i = 0; i < 2; ++i) {
     const int m = m0 + (tid >> 3) + 64 * i;
-    pin[i] = m < a.M;
-    pm[i] = pin[i] ? m : 0;
+    const bool pin = m < a.M;
+    pm[i] = pin ? m : 0;
     const int r = pm[i] % HW;
-    ph[i] = r / a.W;
-    pw[i] = r % a.W;
+    const int ph = r / a.W, pw = r % a.W;
+    inside[i] = 0;
+#pragma unroll
+    for (int t = 0; t < 9; ++t) {
+      const int h = ph + t / 3 - 1, w = pw + t % 3 - 1;
+      inside[i] |= (pin && h >= 0 && h < a.H && w >= 0 && w < a.W ? 1u : 0u) << t;
+    }
   }
   f32x4 xr[2];
   u32x4 wr[4];
   int bad = 0;
 
-  auto load = [&](int s) {
-    const int tap = s / CB, cb = s - tap * CB;
-    const int dy = tap / 3 - 1, dx = tap % 3 - 1;
+  // K is walked tap by tap, and inside a tap channel block by channel block.  What depends on the tap alone is set once per tap:
+  // whether the pixel's tap lies inside the map, and the address of its first channel block.  A tap outside the map reads the
+  // pixel itself instead (an address inside the tensor, whatever the tap) and the loaded values are replaced by zeros, so the load
+  // has no branch.  Per step only the two uniform bases move: the activations' by 32 channels, the weights' by one step's pack.
+  const float* xb = a.x;   // + the channel block (uniform)
+  unsigned xo[2];          // the tap's pixel x Cin + the thread's channels, in elements (M x Cin < 2^31)
+  bool in[2];
+  const u32x4* wsrc = reinterpret_cast<const u32x4*>(a.wp);   // the step's pack (uniform)
+  auto set_tap = [&](int tap) {
+    const int d = (tap / 3 - 1) * a.W + (tap % 3 - 1);
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
-      const int h = ph[i] + dy, w = pw[i] + dx;
-      if (pin[i] && h >= 0 && h < a.H && w >= 0 && w < a.W) {
-        const size_t off = (size_t)(pm[i] + dy * a.W + dx) * a.Cin + cb * kKT + 4 * c4;
-        xr[i] = *reinterpret_cast<const f32x4*>(a.x + off);
-      } else {
-        xr[i] = f32x4{0.f, 0.f, 0.f, 0.f};
-      }
+      in[i] = (inside[i] >> tap) & 1;
+      xo[i] = (unsigned)(pm[i] + (in[i] ? d : 0)) * a.Cin + 4 * c4;
     }
-    const u32x4* wsrc = reinterpret_cast<const u32x4*>(a.wp) + (size_t)s * (2 * kWPlane / 8);
+    xb = a.x;
+  };
+  auto load = [&] {       // the next step's operands, activations first: the MFMA block waits for them alone half way
 #pragma unroll
-    for (int i = 0; i < 4; ++i) wr[i] = wsrc[tid + kThreads * i];
+    for (int i = 0; i < 2; ++i) {
+      xr[i] = *reinterpret_cast<const f32x4*>(xb + xo[i]);
+    }
+    xb += kKT;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) wr[i] = wsrc[(unsigned)(tid + kThreads * i)];
+    wsrc += 2 * kWPlane / 8;
   };
 
-  auto store = [&](int s, _Float16* buf) {
-    const bool centre = s / CB == 4;
+  // RELU: a.relu_in, CENTRE: the tap is the centre tap (the one that counts) -- both uniform over a tap, so the element loop has
+  // neither test
+  auto store_x = [&](auto relu, auto centre, _Float16* buf) __attribute__((always_inline)) {
     _Float16* xh = buf;
     _Float16* xl = buf + kXPlane;
-    _Float16* wb = buf + 2 * kXPlane;
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
       half4 hi, lo;
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
-        float v = xr[i][e];
-        if (a.relu_in) v = v < 0.0f ? 0.0f : v;          // (keeps NaN: it is counted below)
+        float v = in[i] ? xr[i][e] : 0.0f;
+        if constexpr (decltype(relu)::value) v = v < 0.0f ? 0.0f : v;          // (keeps NaN: it is counted below)
         const float y = v * kActScale;
-        bad += (centre && !(fabsf(y) <= kF16Max)) ? 1 : 0;
+        if constexpr (decltype(centre)::value) bad += !(fabsf(y) <= kF16Max) ? 1 : 0;
         const float c = fminf(fmaxf(y, -kF16Max), kF16Max);   // NaN -> -65504 (saturated, counted)
         const _Float16 h = (_Float16)c;
         hi[e] = h;
@@ -141,6 +168,9 @@ __global__ __launch_bounds__(kThreads) void conv3x3_split(ConvArgs a) {
       *reinterpret_cast<half4*>(xh + o) = hi;
       *reinterpret_cast<half4*>(xl + o) = lo;
     }
+  };
+  auto store_w = [&](_Float16* buf) {
+    _Float16* wb = buf + 2 * kXPlane;
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       const int q = tid + kThreads * i;
@@ -157,11 +187,16 @@ __global__ __launch_bounds__(kThreads) void conv3x3_split(ConvArgs a) {
 #pragma unroll
     for (int j = 0; j < 4; ++j) acc[i][j] = accx[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-  load(0);
-  store(0, lds);
+  set_tap(0);
+  load();
+  if (a.relu_in)
+    store_x(Flag<true>{}, Flag<false>{}, lds);
+  else
+    store_x(Flag<false>{}, Flag<false>{}, lds);
+  store_w(lds);
   __syncthreads();
   const int fr = lane & 15, fc = lane >> 4;
-  auto mma = [&](const _Float16* cur) {
+  auto mma = [&](const _Float16* __restrict__ cur, auto&& halfway) __attribute__((always_inline)) {
     const _Float16* xh = cur;
     const _Float16* xl = cur + kXPlane;
     const _Float16* wh = cur + 2 * kXPlane;
@@ -184,20 +219,59 @@ __global__ __launch_bounds__(kThreads) void conv3x3_split(ConvArgs a) {
       for (int i = 0; i < 4; ++i) accx[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bl[i], accx[i][j], 0, 0, 0);
 #pragma unroll
       for (int i = 0; i < 4; ++i) accx[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(al, bh[i], accx[i][j], 0, 0, 0);
+      if (j == 1) halfway();
     }
   };
-  // Steps 0 .. steps-2 prefetch their successor; the last step is apart, so that the loop body has no branch around the loads
-  // and the stores: with one, the compiler cannot tell at the loop's head which loads are still in flight and waits for the
-  // activation loads before it issues the weight loads and the MFMAs.
-  for (int s = 0; s + 1 < steps; ++s) {
-    load(s + 1);
-    __builtin_amdgcn_sched_barrier(0);     // (all of the step's global loads are in flight before its first MFMA ...
-    mma(lds + (s & 1) * kBufHalves);
-    __builtin_amdgcn_sched_barrier(0);     //  ... and nothing that waits for them is moved in among the MFMAs)
-    store(s + 1, lds + ((s + 1) & 1) * kBufHalves);
-    __syncthreads();
-  }
-  mma(lds + ((steps - 1) & 1) * kBufHalves);
+  // The loop runs over the steps that are PREFETCHED, 1 .. steps-1 in K order, and multiplies the step before; the last step is
+  // apart, so that the loop body has no branch around the loads and the stores: with one, the compiler cannot tell at the loop's
+  // head which loads are still in flight and waits for the activation loads before it issues the weight loads and the MFMAs.
+  // All of a step's global loads are issued before its first MFMA (the first fence).  Half way through the MFMAs the next step's
+  // activations are split and written to the other buffer.  That block opens with a fence: left free, the compiler moves the whole
+  // split in front of the step's first MFMA and waits for the activation loads there, which undoes the prefetch.  Behind the fence
+  // the 24 sched_group_barrier pairs place the split's VALU work and the X-plane ds_writes BETWEEN the MFMAs of the second half,
+  // one MFMA to three VALU instructions, where the matrix pipe covers them; with the fence alone they stay in one block between
+  // the two halves.  The wait there is for the two activation loads only, the four weight loads stay in flight until the last MFMA
+  // is issued (the last fence keeps their wait and their ds_writes behind it).  Writing the other buffer at any point of a step is
+  // safe: its last readers were the MFMAs of the step before, and they finished before the barrier that ended that step -- which
+  // is also what lets mma() take its source buffer as restrict: without it the fragment reads of the second half, and with them
+  // its MFMAs, are ordered behind the X-plane writes and nothing overlaps.
+  int par = 0;            // the buffer of the step that is multiplied
+  auto run_taps = [&](auto relu, auto centre, int t0, int t1) __attribute__((always_inline)) {
+#pragma unroll 1
+    for (int tap = t0; tap < t1; ++tap) {
+      if (tap) set_tap(tap);
+      const int n = tap ? CB : CB - 1;       // (tap 0's first block was the prologue's)
+      for (int k = 0; k < n; ++k) {
+        _Float16* nxt = lds + (par ^ 1) * kBufHalves;
+        load();
+        __builtin_amdgcn_sched_barrier(0);
+        mma(lds + par * kBufHalves, [&] {
+          __builtin_amdgcn_sched_barrier(0);
+          store_x(relu, centre, nxt);
+        });
+#pragma unroll
+        for (int g = 0; g < 24; ++g) {
+          __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);     // one MFMA,
+          __builtin_amdgcn_sched_group_barrier(0x002, 3, 0);     // three VALU instructions of the split
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        store_w(nxt);
+        __syncthreads();
+        par ^= 1;
+      }
+    }
+  };
+  // taps 0 .. 3, the centre tap, taps 5 .. 8: one after the other, and all of it once with and once without the input ReLU
+  auto run = [&](auto relu) __attribute__((always_inline)) {
+    run_taps(relu, Flag<false>{}, 0, 4);
+    run_taps(relu, Flag<true>{}, 4, 5);
+    run_taps(relu, Flag<false>{}, 5, 9);
+  };
+  if (a.relu_in)
+    run(Flag<true>{});
+  else
+    run(Flag<false>{});
+  mma(lds + par * kBufHalves, [] {});
 
   // epilogue: D[co][px] -- lane holds pixel fr of each 16-pixel tile and the 4 consecutive channels 4*fc .. of each
   // 16-channel tile, i.e. one float4 of NHWC memory per (tile pair).
