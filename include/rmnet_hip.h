@@ -373,6 +373,35 @@ int rmnet_flow_conv_f32(const float *x, int x_ld, const void *wpack, const float
                         int W, int Cin, int Cout, int ksize, int stride, float *out, int out_ld, int coff, int32_t *range_word,
                         void *stream);
 
+/* C2 TinyFlowNet's flow heads (additive exports, same ABI version): out = conv3x3_p1(x[..., :Cin], w) + bias with two output channels
+ * in plain fp32 FMA, straight from a channel-padded concatenation buffer (csrc/flow_head.hip).  Replaces predict_flow5 ..
+ * predict_flow2 of TinyFlowNet (models/tiny_flownet.py) and the layout copy behind them.  No window and no range word.
+ *   x     [N, H, W, x_ld] fp32 (channels-last), 16-byte aligned; x_ld % 4 == 0, x_ld >= Cin >= 1.  Channels Cin .. x_ld-1 are never
+ *         used: any bit pattern, NaN included;
+ *   wpack fp32 [ceil32(Cin)][9][2] (rmnet_amd.ops.flow_head_pack): w[co][c][ky][kx], unrounded, at (c * 9 + 3 * ky + kx) * 2 + co;
+ *         zero for c >= Cin (ceil32: rounded up to a multiple of 32);
+ *   bias  [2] fp32;  out [N, 2, H, W] fp32 NCHW;
+ *   workspace: 16-byte aligned, at least rmnet_flow_head_workspace_bytes(N, H, W, Cin) bytes (0 for a non-positive size): the
+ *         partial sums [ceil32(Cin) / 32][N][2][H][W] fp32 of the 32-channel slices.
+ * Order of summation: the 32 channels of a slice per tap in channel order (FMA), the nine taps of a slice in the order ky, kx, then
+ * bias + slice 0 + slice 1 + ...: fixed by Cin alone, no atomics -- the same bits from call to call and for any N.
+ * RMNET_E_INVALID_ARG for a NULL pointer, a misaligned x or workspace, a workspace that is too small, and the size rules above;
+ * RMNET_E_UNSUPPORTED for N*H*W*x_ld >= 2^31. */
+size_t rmnet_flow_head_workspace_bytes(int N, int H, int W, int Cin);
+int rmnet_flow_head_f32(const float *x, int x_ld, const float *wpack, const float *bias, int N, int H, int W, int Cin, float *out,
+                        void *workspace, size_t workspace_bytes, void *stream);
+
+/* C2 TinyFlowNet's flow upsamplers (additive export, same ABI version): ConvTranspose2d(2, 2, 4, stride 2, padding 1, no bias) of a
+ * flow head's output, written into the next concatenation buffer in place (csrc/flow_head.hip).  Replaces upsampled_flow5_to_4 ..
+ * upsampled_flow3_to_2 (models/tiny_flownet.py), the copy of their result into the buffer and the zero fill of its padding channels.
+ *   flow  [N, 2, h, w] fp32 NCHW;  w [2][2][4][4] fp32: [ci][co][ky][kx], NCHW-contiguous;
+ *   out   [N, 2h, 2w, out_ld] fp32 (channels-last), 16-byte aligned: channels coff, coff+1 of every pixel get the result, channels
+ *         coff+2 .. out_ld-1 are set to +0.0, no other byte is written.  out_ld % 4 == 0, coff % 4 == 0, coff + 2 <= out_ld.
+ * Output pixel (2i+a, 2j+b), channel co = sum over ci, ty, tx (in that order, FMA) of flow[ci][i+a-1+ty][j+b-1+tx] *
+ * w[ci][co][3-a-2ty][3-b-2tx], taps outside the map skipped: the four phases of rmnet_flow_conv_f32.
+ * RMNET_E_INVALID_ARG for a NULL pointer, a misaligned out and the size rules above; RMNET_E_UNSUPPORTED for N*2h*2w*out_ld >= 2^31. */
+int rmnet_flow_up_f32(const float *flow, const float *w, int N, int h, int w_, float *out, int out_ld, int coff, void *stream);
+
 /* P3/P4 tail: decoder logits -> foreground probability -> soft aggregation -> un-pad (-> soft-max over
  * the K mask channels) in one pass.  dec [n_tot,2,Hp,Wp]: 2-class logits of the objects in flight;
  * clip b owns objects [obj_begin[b], obj_begin[b+1]) (device int32 [B+1]); logit / prob [B,K,H,W] with

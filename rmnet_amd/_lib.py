@@ -94,6 +94,12 @@ SIGNATURES = {
     'rmnet_flow_conv_f32': (ctypes.c_int, [
         c_f32p, ctypes.c_int, ctypes.c_void_p, c_f32p, c_f32p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
         ctypes.c_int, ctypes.c_int, ctypes.c_int, c_f32p, ctypes.c_int, ctypes.c_int, c_i32p, ctypes.c_void_p]),
+    'rmnet_flow_head_workspace_bytes': (ctypes.c_size_t, [ctypes.c_int] * 4),
+    'rmnet_flow_head_f32': (ctypes.c_int, [
+        c_f32p, ctypes.c_int, c_f32p, c_f32p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_f32p, ctypes.c_void_p,
+        ctypes.c_size_t, ctypes.c_void_p]),
+    'rmnet_flow_up_f32': (ctypes.c_int, [
+        c_f32p, c_f32p, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_f32p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
     'rmnet_flow_affine_f32': (ctypes.c_int, [
         c_f32p, c_f32p, c_f32p, ctypes.c_int, ctypes.c_int, c_f32p, ctypes.c_void_p]),
     'rmnet_flow_affine_workspace_bytes': (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int]),

@@ -838,6 +838,90 @@ def flow_conv(x, wpack, w_unscale, shift=None, *, ksize=3, stride=1, transposed=
     return out
 
 
+FLOW_HEAD_SLICE = 32              # csrc/flow_head.hip kCS: input channels per workgroup; the pack is padded to a multiple of it
+
+
+@torch.no_grad()
+def flow_head_pack(weight):
+    """[2, Cin, 3, 3] fp32 flow-head weight (any memory format) -> wpack fp32 [ceil32(Cin) * 9 * 2] in the layout of
+    include/rmnet_hip.h (rmnet_flow_head_f32): weight[co][c][ky][kx], unrounded, at (c * 9 + 3 * ky + kx) * 2 + co, zero for
+    c >= Cin."""
+    if not isinstance(weight, torch.Tensor) or weight.dim() != 4 or weight.shape[0] != 2 or tuple(weight.shape[2:]) != (3, 3) \
+            or weight.shape[1] < 1:
+        raise RuntimeError('flow_head_pack needs a [2, Cin, 3, 3] weight, got %s' % (tuple(getattr(weight, 'shape', ())),))
+    if weight.dtype != torch.float32:
+        raise RuntimeError('flow_head_pack needs fp32 weights, got %s' % weight.dtype)
+    cin = weight.shape[1]
+    cp = (cin + FLOW_HEAD_SLICE - 1) // FLOW_HEAD_SLICE * FLOW_HEAD_SLICE
+    pack = torch.zeros(cp, 9, 2, dtype=torch.float32, device=weight.device)
+    pack[:cin] = weight.detach().permute(1, 2, 3, 0).reshape(cin, 9, 2)
+    return pack.view(-1)
+
+
+def flow_head(x, wpack, bias, cin=None):
+    """conv3x3_p1(x[:, :cin], w) + bias with two output channels in plain fp32 FMA (csrc/flow_head.hip) -> NCHW-contiguous
+    [N, 2, H, W].  ``x`` is a channels-last fp32 [N, x_ld, H, W] tensor of which the first ``cin`` channels (default: all) are the
+    input, x_ld % 4 == 0; what the channels cin .. x_ld - 1 hold does not matter (NaN included).  ``wpack`` comes from
+    ``flow_head_pack`` of a [2, cin, 3, 3] weight, ``bias`` is fp32 [2].  The result has a fixed order of summation: the same bits
+    from call to call and for any N.  No fall-back: anything else is a RuntimeError."""
+    _check_act(x, 'x')
+    if x.dim() != 4 or not x.is_contiguous(memory_format=torch.channels_last):
+        raise RuntimeError('x must be a channels-last [N, C, H, W] tensor')
+    N, x_ld, H, W = x.shape
+    cin = x_ld if cin is None else int(cin)
+    if cin <= 0 or x_ld % 4 or x_ld < cin:
+        raise RuntimeError('flow_head needs x_ld %% 4 == 0 and x_ld >= cin >= 1: x has %d channels for cin = %d' % (x_ld, cin))
+    _check(wpack, 'wpack')
+    want = (cin + FLOW_HEAD_SLICE - 1) // FLOW_HEAD_SLICE * FLOW_HEAD_SLICE * 18
+    if wpack.numel() != want:
+        raise RuntimeError('wpack has %d elements, a cin = %d flow-head pack has %d' % (wpack.numel(), cin, want))
+    _check(bias, 'bias')
+    if bias.numel() != 2:
+        raise RuntimeError('bias must have 2 elements')
+    if wpack.device != x.device or bias.device != x.device:
+        raise RuntimeError('flow_head: every tensor must be on %s' % x.device)
+    if N == 0 or H == 0 or W == 0:
+        raise RuntimeError('flow_head needs a non-empty x, got %s' % (tuple(x.shape),))
+    out = torch.empty((N, 2, H, W), dtype=x.dtype, device=x.device)
+    lib = _lib.load()
+    with torch.cuda.device(x.device):
+        nb = lib.rmnet_flow_head_workspace_bytes(N, H, W, cin)
+        ws = _ws(nb, x.device)
+        rc = lib.rmnet_flow_head_f32(_ptr(x), x_ld, _ptr(wpack), _ptr(bias), N, H, W, cin, _ptr(out), _ptr(ws), nb, _stream(x.device))
+    _lib.check(rc, 'rmnet_flow_head_f32')
+    return out
+
+
+def flow_up(flow, weight, out, coff):
+    """ConvTranspose2d(2, 2, 4, stride 2, padding 1, bias=False) of ``flow`` [N, 2, h, w] (NCHW fp32, a flow head's output) with
+    ``weight`` [2, 2, 4, 4] (NCHW-contiguous), written into the channels ``coff, coff + 1`` of the channels-last fp32 buffer ``out``
+    [N, out_ld, 2h, 2w]; the channels ``coff + 2 .. out_ld - 1`` are set to +0.0 and nothing else is written (csrc/flow_head.hip).
+    out_ld % 4 == 0, coff % 4 == 0, coff + 2 <= out_ld.  Returns ``out``.  No fall-back: anything else is a RuntimeError."""
+    _check(flow, 'flow')
+    if flow.dim() != 4 or flow.shape[1] != 2:
+        raise RuntimeError('flow must be [N, 2, h, w]')
+    N, _, h, w = flow.shape
+    if N == 0 or h == 0 or w == 0:
+        raise RuntimeError('flow_up needs a non-empty flow, got %s' % (tuple(flow.shape),))
+    _check(weight, 'weight')
+    if tuple(weight.shape) != (2, 2, 4, 4):
+        raise RuntimeError('flow_up needs a [2, 2, 4, 4] weight, got %s' % (tuple(weight.shape),))
+    _check_act(out, 'out')
+    if out.dim() != 4 or not out.is_contiguous(memory_format=torch.channels_last) or \
+            (out.shape[0], out.shape[2], out.shape[3]) != (N, 2 * h, 2 * w):
+        raise RuntimeError('out must be a channels-last [%d, out_ld, %d, %d] tensor' % (N, 2 * h, 2 * w))
+    coff = int(coff)
+    if out.shape[1] % 4 or coff % 4 or coff < 0 or coff + 2 > out.shape[1]:
+        raise RuntimeError('flow_up needs out_ld %% 4 == 0, coff %% 4 == 0 and coff + 2 <= out_ld, got %d, %d' % (out.shape[1], coff))
+    if weight.device != flow.device or out.device != flow.device:
+        raise RuntimeError('flow_up: every tensor must be on %s' % flow.device)
+    lib = _lib.load()
+    with torch.cuda.device(flow.device):
+        rc = lib.rmnet_flow_up_f32(_ptr(flow), _ptr(weight), N, h, w, _ptr(out), out.shape[1], coff, _stream(flow.device))
+    _lib.check(rc, 'rmnet_flow_up_f32')
+    return out
+
+
 STEM_COUT = 64                    # csrc/stem.hip: output channels of the encoder stems
 
 

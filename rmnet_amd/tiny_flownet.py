@@ -1,6 +1,7 @@
 # -*- coding: utf-8 -*-
 """TinyFlowNet on stock PyTorch-ROCm; on a fused channels-last network its ten wide convolutions run
-on a HIP kernel (csrc/flow_conv.hip, ``RMNET_FLOW_CONV``: see ``TinyFlowNet._forward``).
+on a HIP kernel (csrc/flow_conv.hip, ``RMNET_FLOW_CONV``: see ``TinyFlowNet._forward``), and with ``RMNET_FLOW_CONV=full`` its four
+flow heads and three flow upsamplers as well (csrc/flow_head.hip).
 
 Mirrors ``models/tiny_flownet.py`` of the reference: same constructor signature, same
 ``forward(frames) -> [B, N, 2, H, W]`` contract and the same state-dict keys
@@ -49,10 +50,11 @@ _CAT_LD = {4: 800, 3: 416, 2: 224}
 
 def flow_conv_backend():
     """RMNET_FLOW_CONV (A/B switch, read at every call): 'split' (default) -- the ten wide convolutions of a fused, channels-last
-    TinyFlowNet run on the split-fp16 HIP kernel; 'miopen' -- none does."""
+    TinyFlowNet run on the split-fp16 HIP kernel; 'full' -- so do they, and the four flow heads and the three flow upsamplers run on
+    csrc/flow_head.hip, which leaves conv1 as the network's only library convolution; 'miopen' -- none does."""
     v = os.environ.get('RMNET_FLOW_CONV', FLOW_CONV_DEFAULT).lower()
-    if v not in ('split', 'miopen'):
-        raise RuntimeError('RMNET_FLOW_CONV must be split or miopen, got %r' % v)
+    if v not in ('split', 'full', 'miopen'):
+        raise RuntimeError('RMNET_FLOW_CONV must be split, full or miopen, got %r' % v)
     return v
 
 
@@ -89,13 +91,15 @@ class TinyFlowNet(nn.Module):
         saturates activations outside |x| < 1023.5 and counts them in ``flow_range_word(device)``.  There is no host
         synchronisation here (the call can be captured into a HIP graph): ``forward`` zeroes and checks the word once per clip, a
         streaming caller of ``_forward`` checks ``flow_range_count()`` itself and, when it is non-zero, zeroes the word and redoes
-        the frames since its last check with ``RMNET_FLOW_CONV=miopen``."""
+        the frames since its last check with ``RMNET_FLOW_CONV=miopen``.  ``RMNET_FLOW_CONV=full`` runs the flow heads and the flow
+        upsamplers on csrc/flow_head.hip as well (plain fp32, no window): conv1 is then the only library convolution."""
         (img0, img1), pad = pad_divide_by([img0, img1], 64, img0.shape[2:])
         pair = torch.cat((F.interpolate(img0, scale_factor=0.5, mode='bilinear'),
                           F.interpolate(img1, scale_factor=0.5, mode='bilinear')), dim=1)
         run = self._fused_block if getattr(self, '_fused', False) and not self.training and pair.is_cuda else (lambda m, x: m(x))
-        if self._flow_split_ok(pair):
-            flow2 = self._refine_split(run(self.conv1, pair))
+        backend = self._flow_split_ok(pair)
+        if backend:
+            flow2 = self._refine_split(run(self.conv1, pair), full=backend == 'full')
         else:
             c2 = run(self.conv2, run(self.conv1, pair))
             c3 = run(self.conv3_1, run(self.conv3, c2))
@@ -117,8 +121,9 @@ class TinyFlowNet(nn.Module):
 
     # ------------------------------------------------------------------------------------------ the split-fp16 path
     def _flow_split_ok(self, pair):
-        """The ten wide convolutions run on csrc/flow_conv.hip for this input: fused with packs on the input's device, eval, CUDA
-        fp32, a channels-last run, RMNET_FLOW_CONV not miopen, and not the MIOpen re-run of a clip that left the window."""
+        """'split' or 'full' when the ten wide convolutions run on csrc/flow_conv.hip for this input (the value of RMNET_FLOW_CONV),
+        else False: fused with packs on the input's device, eval, CUDA fp32, a channels-last run, RMNET_FLOW_CONV not miopen, and
+        not the MIOpen re-run of a clip that left the window."""
         if not getattr(self, '_fused', False) or self.training or getattr(self, '_flow_off', False):
             return False
         packs = getattr(self, '_flow_packs', None)
@@ -127,19 +132,23 @@ class TinyFlowNet(nn.Module):
         from .ops import _is_cl
         if not (_is_cl(pair) or _is_cl(self.conv2[0].weight)):
             return False
-        return flow_conv_backend() == 'split'
+        backend = flow_conv_backend()
+        return backend if backend in ('split', 'full') else False
 
-    def _refine_split(self, c1):
+    def _refine_split(self, c1, full=False):
         """conv2 .. predict_flow2 on ``c1`` = conv1's output, the ten wide layers on the HIP kernel.  cat4 / cat3 / cat2 are ONE
         channels-last buffer each (800 / 416 / 224 channels per pixel): conv4_1 / conv3_1 / conv2 write the channels from 0, the
         deconvolutions theirs from 512 / 256 / 128, torch copies the two upsampled-flow channels behind them, and the padding up to
         the next multiple of 32 is zeroed -- so no torch.cat is left.  The flow heads of the three buffers convolve the WHOLE buffer
         with a zero-padded copy of their weight (``fuse_epilogues``): a channel-sliced view would be copied into a dense tensor
         by the library first.  Every buffer is a fresh stream-ordered allocation: nothing is kept between calls, and nothing
-        depends on the frame, so the call can be captured."""
+        depends on the frame, so the call can be captured.
+        ``full``: the flow heads run on csrc/flow_head.hip, which reads the first 512 / 770 / 386 / 194 channels of c5 / cat4 / cat3 /
+        cat2 with the heads' own weights (packed), and the upsamplers on its flow_up, which writes the two flow channels at 768 / 384 /
+        192 of the next buffer and zeroes the padding behind them: no library call, no copy and no zero fill is left."""
         from . import ops
         word = self.flow_range_word(c1.device)
-        self.__dict__['_flow_used'] = True            # (for ``forward``: a host flag, no synchronisation)
+        self.__dict__['_flow_used'] = 'full' if full else 'split'            # (for ``forward``: a host flag, no synchronisation)
 
         def fc(name, x, cin=None, out=None, coff=0):
             conv = getattr(self, name)[0]
@@ -157,6 +166,12 @@ class TinyFlowNet(nn.Module):
             cat[:, real - 2:real].copy_(up)           # the upsampled flow, behind the deconvolution's channels
             cat[:, real:].zero_()                     # the padding: finite for the kernel (zero weights), ZERO for the flow head
 
+        def head(level, x, cin):
+            return ops.flow_head(x, self._flow_head_packs[level], getattr(self, 'predict_flow%d' % level).bias, cin=cin)
+
+        def up(level, flow, cat, real):               # flow_up writes the two channels and the zero padding behind them
+            ops.flow_up(flow, self._flow_up_w[level], cat, real - 2)
+
         c1 = c1.contiguous(memory_format=torch.channels_last)      # (no copy in a channels-last run)
         cat2 = buf(2, c1)
         fc('conv2', c1, out=cat2)
@@ -166,6 +181,14 @@ class TinyFlowNet(nn.Module):
         fc('conv4_1', fc('conv4', cat3, cin=256), out=cat4)
         c5 = fc('conv5_1', fc('conv5', cat4, cin=512))
 
+        if full:
+            fc('deconv4', c5, out=cat4, coff=512)
+            up(4, head(5, c5, 512), cat4, 770)
+            fc('deconv3', cat4, cin=770, out=cat3, coff=256)
+            up(3, head(4, cat4, 770), cat3, 386)
+            fc('deconv2', cat3, cin=386, out=cat2, coff=128)
+            up(2, head(3, cat3, 386), cat2, 194)
+            return head(2, cat2, 194)
         fc('deconv4', c5, out=cat4, coff=512)
         tail(cat4, 770, self.upsampled_flow5_to_4(self.predict_flow5(c5)))
         fc('deconv3', cat4, cin=770, out=cat3, coff=256)
@@ -196,8 +219,9 @@ class TinyFlowNet(nn.Module):
 
     @torch.no_grad()
     def _build_flow_packs(self):
-        """The ten weight packs, the zero-padded flow-head weights and the range word: plain attributes (not parameters or buffers,
-        so ``state_dict()`` is untouched), rebuilt whenever the parameters move (``_apply``) or are loaded."""
+        """The ten weight packs, the zero-padded flow-head weights, the four flow-head packs and NCHW-contiguous upsampler weights
+        of csrc/flow_head.hip, and the range word: plain attributes (not parameters or buffers, so ``state_dict()`` is untouched),
+        rebuilt whenever the parameters move (``_apply``) or are loaded."""
         from . import ops
         packs = {}
         for name in FLOW_SPLIT_LAYERS:
@@ -209,6 +233,10 @@ class TinyFlowNet(nn.Module):
             heads[level] = F.pad(w, (0, 0, 0, 0, 0, ld - w.shape[1])).contiguous(memory_format=torch.channels_last)
         self.__dict__['_flow_packs'] = packs
         self.__dict__['_flow_head_w'] = heads
+        self.__dict__['_flow_head_packs'] = {level: ops.flow_head_pack(getattr(self, 'predict_flow%d' % level).weight.detach().float())
+                                             for level in (5, 4, 3, 2)}
+        self.__dict__['_flow_up_w'] = {level: getattr(self, 'upsampled_flow%d_to_%d' % (level + 1, level)).weight.detach().float()
+                                       .contiguous().clone() for level in (4, 3, 2)}
         if self.conv1[0].weight.is_cuda:
             self.flow_range_word(self.conv1[0].weight.device)
 
@@ -244,7 +272,8 @@ class TinyFlowNet(nn.Module):
 
     def fuse_epilogues(self, enable=True):
         """Bias + LeakyReLU of every block as one kernel (parameters untouched), and the weight packs of the ten wide convolutions
-        for the split-fp16 kernel (plain attributes: ``state_dict()`` is unchanged; ``RMNET_FLOW_CONV=miopen`` leaves them unused)."""
+        for the split-fp16 kernel and of the flow heads and upsamplers for csrc/flow_head.hip (plain attributes: ``state_dict()`` is
+        unchanged; ``RMNET_FLOW_CONV=miopen`` leaves them unused)."""
         self.eval()
         self._fused = bool(enable)
         if self._fused:
@@ -252,6 +281,8 @@ class TinyFlowNet(nn.Module):
         else:
             self.__dict__.pop('_flow_packs', None)
             self.__dict__.pop('_flow_head_w', None)
+            self.__dict__.pop('_flow_head_packs', None)
+            self.__dict__.pop('_flow_up_w', None)
         return self
 
     def forward(self, frames, device=None):
@@ -264,7 +295,7 @@ class TinyFlowNet(nn.Module):
             self.flow_range_word(frames.device).zero_()
         self.__dict__['_flow_used'] = False
         flows = self._clip(frames)
-        split = self.__dict__['_flow_used']          # some frame pair took the split-fp16 path
+        split = self.__dict__['_flow_used']          # some frame pair took the split-fp16 path: 'split' or 'full'
         count = self.flow_range_count(frames.device) if split else 0
         if count:
             self.__dict__['_flow_off'] = True
@@ -272,7 +303,7 @@ class TinyFlowNet(nn.Module):
                 flows = self._clip(frames)
             finally:
                 self.__dict__['_flow_off'] = False
-        self.__dict__['last_clip'] = {'flow_conv': 'split' if split and not count else 'miopen', 'range': count}
+        self.__dict__['last_clip'] = {'flow_conv': split if split and not count else 'miopen', 'range': count}
         return flows
 
     def _clip(self, frames):
