@@ -316,6 +316,34 @@ int rmnet_conv_split_f32(const float *x, const void *wpack, const float *w_unsca
                          int N, int H, int W, int Cin, int Cout, int ksize, int stride, float *out, float *out2, int out_split,
                          int32_t *range_word, void *stream);
 
+/* C1 pre-split activations (additive export, same ABI version).  rmnet_conv_split_f32 splits every activation it reads at every tap
+ * and in every Cout tile; the split depends on the element alone, so a tensor that only such convolutions read can be kept in split
+ * form and split once (csrc/conv_split.hip: conv_split_pre, split_act).
+ *
+ * The split ACTIVATION form of an NHWC activation v [M][C] fp32, C % 32 == 0, is [M][C / 32][2][32] fp16: per pixel and block of 32
+ * channels the 32 hi halves, then the 32 lo halves, of
+ *     y = pre(v) * 64;  c = fminf(fmaxf(y, -65504), 65504);  hi = (fp16)c;  lo = (fp16)(c - (float)hi)
+ * (pre = an optional ReLU that keeps NaN; float32 arithmetic, round to nearest even; hi + lo == c to 2^-22 relative).  It has 4 bytes
+ * per element like fp32, a pixel has the same byte stride, and every aligned 16-byte chunk holds 8 halves of one plane.  An element
+ * with !(fabsf(y) <= 65504) adds one to the range word where the form is PRODUCED, once; a consumer counts nothing.
+ *
+ * rmnet_conv_split_pre_f32: rmnet_conv_split_f32 with two more flag bits -- the same tiles, arithmetic, K order, epilogue and results.
+ *   RMNET_CONV_X_SPLIT    x is in split form.  RMNET_CONV_RELU_IN is then refused (the producer applied it), and the convolution
+ *                         adds nothing to the range word for its input;
+ *   RMNET_CONV_OUT_SPLIT  out receives act(conv + shift + res) in split form instead of fp32 and the elements of it outside the
+ *                         window are counted.  out2 must be NULL, and out must overlap neither x nor res (an fp32 out may still BE
+ *                         res).
+ *   With neither bit the call is rmnet_conv_split_f32's.  Other argument rules and return codes: as there.
+ * rmnet_split_act_f32: x [M][C] fp32 -> out in split form, ReLU first when relu != 0, for tensors that another kernel produced.
+ *   One grid-stride launch, no LDS.  x and out 16-byte aligned and not overlapping (RMNET_E_INVALID_ARG); RMNET_E_UNSUPPORTED for
+ *   C % 32 != 0. */
+#define RMNET_CONV_X_SPLIT 4
+#define RMNET_CONV_OUT_SPLIT 8
+int rmnet_conv_split_pre_f32(const void *x, const void *wpack, const float *w_unscale, const float *shift, const float *res, int flags,
+                             int N, int H, int W, int Cin, int Cout, int ksize, int stride, void *out, float *out2, int out_split,
+                             int32_t *range_word, void *stream);
+int rmnet_split_act_f32(const float *x, long long M, int C, int relu, void *out, int32_t *range_word, void *stream);
+
 /* C1 encoder stems (additive export, same ABI version): the 7x7 / stride 2 / pad 3 stem convolution, the folded BatchNorm, ReLU and
  * MaxPool2d(3, stride 2, padding 1) in ONE launch (csrc/stem.hip), on the split-fp16 arithmetic of rmnet_conv3x3_split_f32; the
  * half-resolution 64-channel activation is never written.  Replaces conv1 (+ conv1_m + conv1_o) / bn1 / relu / maxpool of both

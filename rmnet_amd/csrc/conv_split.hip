@@ -23,6 +23,10 @@
 // and exactly the declared LDS (96 / 64 / 48 KB).
 // One LDS double buffer (X hi/lo [MT][32] + W hi/lo [NT][32] fp16), one barrier per K step, as in conv3x3.hip.  The next step's
 // operands are prefetched into VGPRs (native vector types: an array of HIP's uint4 would be placed in LDS) while the MFMAs run.
+//
+// conv_split_pre, further down, is a COPY of conv_split (loader, mma, epilogue) that reads and / or writes the split activation form;
+// conv_split's code object is kept as it is, so the two are kept in step by hand: a change to the arithmetic, the K order or the
+// epilogue expressions of one belongs in the other, and tests/test_conv_presplit.py compares them bit for bit.
 #include "common.h"
 
 namespace rmnet {
@@ -301,6 +305,348 @@ void launch(const SplitArgs& a, hipStream_t st) {
                      0, st, a);
 }
 
+// ------------------------------------------------------------------------------------------------ pre-split activations
+// The split ACTIVATION form (include/rmnet_hip.h): [M][C / 32][2][32] fp16 -- per pixel and block of 32 channels the 32 hi halves,
+// then the 32 lo halves, of c = clamp(64 * pre(v)).  A pixel has the byte stride it has in fp32, and every 16-byte chunk is 8 halves of
+// one plane: exactly a chunk of the LDS image.  split4 is store_x's per-element arithmetic, expression for expression.
+__device__ inline void split4(const f32x4 v, half4& hi, half4& lo, int& bad) {
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    const float y = v[e] * kActScale;
+    bad += !(fabsf(y) <= kF16Max) ? 1 : 0;
+    const float c = fminf(fmaxf(y, -kF16Max), kF16Max);
+    const _Float16 h = (_Float16)c;
+    hi[e] = h;
+    lo[e] = (_Float16)(c - (float)h);
+  }
+}
+
+struct PreArgs {
+  const float* x;          // XS 0: [N][H][W][Cin] fp32
+  const _Float16* xs;      // XS 1: [N][H][W][Cin / 32][2][32] fp16
+  const u32x4* wp;
+  const float* unscale;
+  const float* shift;
+  const float* res;        // [M][Cout] fp32 or null
+  float* out;              // OS 0: [M][Cout] fp32, or [M][csplit] with out2
+  float* out2;             // OS 0 only
+  _Float16* outs;          // OS 1: [M][Cout / 32][2][32] fp16
+  int* range;
+  int M, H, W, Ho, Wo, Cin, Cout, csplit, ksize, stride, pad, relu_in, relu_out;
+};
+
+// conv_split with the activations read from the split form (XS) and / or the output written in it (OS); tiles, mma, K order and
+// epilogue expressions are conv_split's.  XS: the loader is a 16-byte load and a 16-byte LDS store per item (thread = pixel
+// tid / 8 + 64 i, chunk tid % 8: plane tid % 8 / 4, channels 8 (tid % 4) ..), nothing is converted, clamped or counted in the loop
+// (the producer did that, once per element), and every tile has all of a step's loads in flight before its first MFMA.  XS 0 keeps
+// store_x's loop, Mid's "in turn" form included.  OS: a lane's 4 channels go out as 8 bytes of hi and 8 bytes of lo, and the
+// elements outside the window are counted here, once each.
+template <int WM, int WN, int TI, int TJ, int WPE, bool XS, bool OS>
+__global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(WPE))) void conv_split_pre(PreArgs a) {
+  static_assert(WM * WN * 64 == kThreads, "8 waves");
+  constexpr int MT = WM * TI * 16, NT = WN * TJ * 16;
+  constexpr int XI = MT / 64;                      // activation items per thread and step (16 bytes each, either form)
+  constexpr int WI = NT / 64;
+  constexpr int kXPlane = MT * kKT, kWPlane = NT * kKT;
+  constexpr int kBufHalves = 2 * kXPlane + 2 * kWPlane;
+  static_assert(2 * kBufHalves * 2 <= kLdsBytesPerCU, "LDS budget");
+  __shared__ __attribute__((aligned(16))) _Float16 lds[2 * kBufHalves];
+
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int wm = wave % WM, wn = wave / WM;
+  const int m0 = blockIdx.x * MT, n0 = blockIdx.y * NT;
+  const int CB = a.Cin / kKT, steps = a.ksize * a.ksize * CB;
+  const int HWo = a.Ho * a.Wo;
+
+  const int c4 = tid & 7;
+  int pbase[XI], ph[XI], pw[XI];
+#pragma unroll
+  for (int i = 0; i < XI; ++i) {
+    const int m = m0 + (tid >> 3) + 64 * i;
+    const int n = m / HWo, r = m - n * HWo;
+    const int ho = r / a.Wo, wo = r - ho * a.Wo;
+    ph[i] = m < a.M ? ho * a.stride - a.pad : -4;
+    pw[i] = wo * a.stride - a.pad;
+    pbase[i] = (n * a.H + ph[i]) * a.W + pw[i];
+  }
+  f32x4 xr[XI];
+  u32x4 xq[XI];
+  u32x4 wr[WI];
+  int bad = 0;
+
+  auto load_x = [&](int s) {
+    const int tap = s / CB, cb = s - tap * CB;
+    const int ky = tap / a.ksize, kx = tap - ky * a.ksize;
+#pragma unroll
+    for (int i = 0; i < XI; ++i) {
+      const int h = ph[i] + ky, w = pw[i] + kx;
+      const bool in = (unsigned)h < (unsigned)a.H && (unsigned)w < (unsigned)a.W;
+      if constexpr (XS) {
+        if (in) {
+          // (in halves, below 2^32: the entry holds N*H*W*Cin below 2^31 -- a uniform base and a 32-bit offset per lane)
+          const unsigned off = (unsigned)(pbase[i] + ky * a.W + kx) * (unsigned)(2 * a.Cin) + (unsigned)(cb * (2 * kKT) + 8 * c4);
+          xq[i] = *reinterpret_cast<const u32x4*>(a.xs + off);
+        } else {
+          xq[i] = u32x4{0u, 0u, 0u, 0u};
+        }
+      } else {
+        if (in) {
+          const size_t off = (size_t)(pbase[i] + ky * a.W + kx) * a.Cin + cb * kKT + 4 * c4;
+          xr[i] = *reinterpret_cast<const f32x4*>(a.x + off);
+        } else {
+          xr[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+        }
+      }
+    }
+  };
+  auto load_w = [&](int s) {
+    const u32x4* wsrc = a.wp + (size_t)s * (a.Cout * 8);
+#pragma unroll
+    for (int i = 0; i < WI; ++i) {
+      const int q = tid + kThreads * i;
+      const int plane = q / (NT * 4), co = (q >> 2) % NT, ch = q & 3;
+      wr[i] = wsrc[(unsigned)(plane * (a.Cout * 4) + (n0 + co) * 4 + ch)];      // (uniform base, 32-bit lane offset)
+    }
+  };
+
+  auto counted = [&](int t) { return t == a.pad || (a.stride == 2 && a.ksize == 3 && t == 2); };
+
+  auto store_x = [&](int s, _Float16* buf) {
+    if constexpr (XS) {
+#pragma unroll
+      for (int i = 0; i < XI; ++i) {
+        const int p = (tid >> 3) + 64 * i;
+        *reinterpret_cast<u32x4*>(buf + (c4 >> 2) * kXPlane + swz(p, c4 & 3)) = xq[i];
+      }
+    } else {
+      const int tap = s / CB, ky = tap / a.ksize, kx = tap - ky * a.ksize;
+      const bool count = blockIdx.y == 0 && counted(ky) && counted(kx);
+      _Float16* xh = buf;
+      _Float16* xl = buf + kXPlane;
+#pragma unroll
+      for (int i = 0; i < XI; ++i) {
+        half4 hi, lo;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          float v = xr[i][e];
+          if (a.relu_in) v = v < 0.0f ? 0.0f : v;
+          const float y = v * kActScale;
+          bad += (count && !(fabsf(y) <= kF16Max)) ? 1 : 0;
+          const float c = fminf(fmaxf(y, -kF16Max), kF16Max);
+          const _Float16 h = (_Float16)c;
+          hi[e] = h;
+          lo[e] = (_Float16)(c - (float)h);
+        }
+        const int p = (tid >> 3) + 64 * i;
+        const int o = swz(p, c4 >> 1) + 4 * (c4 & 1);
+        *reinterpret_cast<half4*>(xh + o) = hi;
+        *reinterpret_cast<half4*>(xl + o) = lo;
+      }
+    }
+  };
+  auto store_w = [&](_Float16* buf) {
+    _Float16* wb = buf + 2 * kXPlane;
+#pragma unroll
+    for (int i = 0; i < WI; ++i) {
+      const int q = tid + kThreads * i;
+      const int plane = q / (NT * 4), co = (q >> 2) % NT, ch = q & 3;
+      *reinterpret_cast<u32x4*>(wb + plane * kWPlane + swz(co, ch)) = wr[i];
+    }
+  };
+
+  f32x4 acc[TI][TJ], accx[TI][TJ];
+#pragma unroll
+  for (int i = 0; i < TI; ++i)
+#pragma unroll
+    for (int j = 0; j < TJ; ++j) acc[i][j] = accx[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+  load_x(0);
+  load_w(0);
+  store_x(0, lds);
+  store_w(lds);
+  __syncthreads();
+  const int fr = lane & 15, fc = lane >> 4;
+  // conv_split's mma, term for term.  A fragment's swizzle depends on its row's bits 1..2 alone, which a step of 16 rows leaves
+  // alone: one address per operand (xo, wo) and constant offsets from it, instead of one address register per fragment
+  const int xo = swz(wm * TI * 16 + fr, fc), wo = 2 * kXPlane + swz(wn * TJ * 16 + fr, fc);
+  constexpr int kFrag = 16 * kKT;
+  auto mma = [&](const _Float16* cur, auto&& halfway) {
+    const _Float16* xb = cur + xo;
+    const _Float16* wb = cur + wo;
+    if constexpr (TJ >= TI) {
+      half8 bh[TI], bl[TI];
+#pragma unroll
+      for (int i = 0; i < TI; ++i) {
+        bh[i] = *reinterpret_cast<const half8*>(xb + i * kFrag);
+        bl[i] = *reinterpret_cast<const half8*>(xb + kXPlane + i * kFrag);
+      }
+#pragma unroll
+      for (int j = 0; j < TJ; ++j) {
+        const half8 ah = *reinterpret_cast<const half8*>(wb + j * kFrag);
+        const half8 al = *reinterpret_cast<const half8*>(wb + kWPlane + j * kFrag);
+#pragma unroll
+        for (int i = 0; i < TI; ++i) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bh[i], acc[i][j], 0, 0, 0);
+#pragma unroll
+        for (int i = 0; i < TI; ++i) accx[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bl[i], accx[i][j], 0, 0, 0);
+#pragma unroll
+        for (int i = 0; i < TI; ++i) accx[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(al, bh[i], accx[i][j], 0, 0, 0);
+        if (j == TJ / 2 - 1) halfway();
+      }
+    } else {
+      half8 ah[TJ], al[TJ];
+#pragma unroll
+      for (int j = 0; j < TJ; ++j) {
+        ah[j] = *reinterpret_cast<const half8*>(wb + j * kFrag);
+        al[j] = *reinterpret_cast<const half8*>(wb + kWPlane + j * kFrag);
+      }
+#pragma unroll
+      for (int i = 0; i < TI; ++i) {
+        const half8 bh = *reinterpret_cast<const half8*>(xb + i * kFrag);
+        const half8 bl = *reinterpret_cast<const half8*>(xb + kXPlane + i * kFrag);
+#pragma unroll
+        for (int j = 0; j < TJ; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[j], bh, acc[i][j], 0, 0, 0);
+#pragma unroll
+        for (int j = 0; j < TJ; ++j) accx[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[j], bl, accx[i][j], 0, 0, 0);
+#pragma unroll
+        for (int j = 0; j < TJ; ++j) accx[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(al[j], bh, accx[i][j], 0, 0, 0);
+        if (i == TI / 2 - 1) halfway();
+      }
+    }
+  };
+  // XS: 16 VGPRs of loads in flight (Mid) and nothing to convert, so no tile takes its loads in turn
+  constexpr bool kInTurn = !XS && TI > TJ && WPE == 4 && WI > 1;
+  for (int s = 0; s + 1 < steps; ++s) {
+    _Float16* nxt = lds + ((s + 1) & 1) * kBufHalves;
+    load_x(s + 1);
+    if constexpr (!kInTurn) load_w(s + 1);
+    __builtin_amdgcn_sched_barrier(0);
+    mma(lds + (s & 1) * kBufHalves, [&] {
+      if constexpr (kInTurn) {
+        __builtin_amdgcn_sched_barrier(0);
+        load_w(s + 1);
+        store_x(s + 1, nxt);
+        __builtin_amdgcn_sched_barrier(0);
+      }
+    });
+    __builtin_amdgcn_sched_barrier(0);
+    if constexpr (!kInTurn) store_x(s + 1, nxt);
+    store_w(nxt);
+    __syncthreads();
+  }
+  mma(lds + ((steps - 1) & 1) * kBufHalves, [] {});
+
+  // epilogue: conv_split's (see there for the order of the reads and the empty statement); a split output never is res
+  f32x4 r[TI][TJ];
+  if (a.res) {
+#pragma unroll
+    for (int i = 0; i < TI; ++i) {
+      const int m = m0 + wm * TI * 16 + i * 16 + fr;
+#pragma unroll
+      for (int j = 0; j < TJ; ++j) {
+        const int co = n0 + wn * TJ * 16 + j * 16 + 4 * fc;
+        r[i][j] = m < a.M ? *reinterpret_cast<const f32x4*>(a.res + (size_t)m * a.Cout + co) : f32x4{0.f, 0.f, 0.f, 0.f};
+      }
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < TJ; ++j) {
+    const int co = n0 + wn * TJ * 16 + j * 16 + 4 * fc;
+    const f32x4 us = *reinterpret_cast<const f32x4*>(a.unscale + co) * kActUnscale;
+    const f32x4 b = a.shift ? *reinterpret_cast<const f32x4*>(a.shift + co) : f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int i = 0; i < TI; ++i) acc[i][j] = (acc[i][j] + accx[i][j]) * us + b;
+  }
+#pragma unroll
+  for (int j = 0; j < TJ; ++j)
+#pragma unroll
+    for (int i = 0; i < TI; ++i) asm volatile("" : "+v"(acc[i][j]));
+#pragma unroll
+  for (int j = 0; j < TJ; ++j) {
+    const int co = n0 + wn * TJ * 16 + j * 16 + 4 * fc;
+#pragma unroll
+    for (int i = 0; i < TI; ++i) {
+      const int m = m0 + wm * TI * 16 + i * 16 + fr;
+      if (m >= a.M) continue;
+      f32x4 v = acc[i][j];
+      if (a.res) v += r[i][j];
+      if (a.relu_out) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) v[e] = v[e] < 0.0f ? 0.0f : v[e];
+      }
+      if constexpr (OS) {
+        half4 hi, lo;
+        split4(v, hi, lo, bad);
+        _Float16* o = a.outs + (size_t)m * (2 * a.Cout) + (co >> 5) * (2 * kKT) + (co & 31);
+        *reinterpret_cast<half4*>(o) = hi;
+        *reinterpret_cast<half4*>(o + kKT) = lo;
+      } else {
+        const size_t off = (size_t)m * a.Cout + co;
+        if (!a.out2)
+          *reinterpret_cast<f32x4*>(a.out + off) = v;
+        else if (co < a.csplit)
+          *reinterpret_cast<f32x4*>(a.out + (size_t)m * a.csplit + co) = v;
+        else
+          *reinterpret_cast<f32x4*>(a.out2 + (size_t)m * (a.Cout - a.csplit) + (co - a.csplit)) = v;
+      }
+    }
+  }
+  if (a.range && bad) atomicAdd(a.range, bad);
+}
+
+template <int WM, int WN, int TI, int TJ, int WPE, bool XS, bool OS>
+void launch_pre(const PreArgs& a, hipStream_t st) {
+  constexpr int MT = WM * TI * 16, NT = WN * TJ * 16;
+  hipLaunchKernelGGL((conv_split_pre<WM, WN, TI, TJ, WPE, XS, OS>), dim3((unsigned)((a.M + MT - 1) / MT), (unsigned)(a.Cout / NT)),
+                     dim3(kThreads), 0, st, a);
+}
+
+template <bool XS, bool OS>
+void launch_pre_tile(const PreArgs& a, hipStream_t st) {      // rmnet_conv_split_f32's choice of tile
+  if (a.Cout % 256 == 0 && (long long)((a.M + 127) / 128) * (a.Cout / 256) >= 512)
+    launch_pre<2, 4, 4, 4, 2, XS, OS>(a, st);
+  else if (a.Cout % 128 == 0)
+    launch_pre<2, 4, 4, 2, 4, XS, OS>(a, st);
+  else
+    launch_pre<4, 2, 2, 2, 4, XS, OS>(a, st);
+}
+
+// fp32 NHWC -> split form, one item = 8 channels of one block: 32 bytes in, 16 bytes of hi and 16 of lo out.  No LDS.
+constexpr int kSplitActThreads = 256;
+__global__ __launch_bounds__(kSplitActThreads) void split_act(const float* __restrict__ x, _Float16* __restrict__ out, size_t items,
+                                                              int relu, int* range) {
+  int bad = 0;
+  for (size_t q = (size_t)blockIdx.x * kSplitActThreads + threadIdx.x; q < items; q += (size_t)gridDim.x * kSplitActThreads) {
+    f32x4 v[2];
+    v[0] = *reinterpret_cast<const f32x4*>(x + q * 8);
+    v[1] = *reinterpret_cast<const f32x4*>(x + q * 8 + 4);
+    half8 hi, lo;
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+      if (relu) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) v[k][e] = v[k][e] < 0.0f ? 0.0f : v[k][e];      // (keeps NaN)
+      }
+      half4 h4, l4;
+      split4(v[k], h4, l4, bad);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        hi[4 * k + e] = h4[e];
+        lo[4 * k + e] = l4[e];
+      }
+    }
+    _Float16* o = out + (q >> 2) * (2 * kKT) + (q & 3) * 8;
+    *reinterpret_cast<half8*>(o) = hi;
+    *reinterpret_cast<half8*>(o + kKT) = lo;
+  }
+  if (range && bad) atomicAdd(range, bad);
+}
+
+inline bool overlap(const void* p, long long pn, const void* q, long long qn) {
+  const char* a = reinterpret_cast<const char*>(p);
+  const char* b = reinterpret_cast<const char*>(q);
+  return a < b + qn && b < a + pn;
+}
+
 }  // namespace
 }  // namespace rmnet
 
@@ -346,5 +692,67 @@ extern "C" int rmnet_conv_split_f32(const float* x, const void* wpack, const flo
     launch<2, 4, 4, 2, 4>(a, st);     // Mid    128 x 128
   else
     launch<4, 2, 2, 2, 4>(a, st);     // Narrow 128 x 64
+  return check_launch();
+}
+
+extern "C" int rmnet_conv_split_pre_f32(const void* x, const void* wpack, const float* w_unscale, const float* shift, const float* res,
+                                        int flags, int N, int H, int W, int Cin, int Cout, int ksize, int stride, void* out, float* out2,
+                                        int out_split, int32_t* range_word, void* stream) {
+  using namespace rmnet;
+  if (flags & ~(RMNET_CONV_RELU_IN | RMNET_CONV_RELU_OUT | RMNET_CONV_X_SPLIT | RMNET_CONV_OUT_SPLIT)) return RMNET_E_INVALID_ARG;
+  const bool xs = (flags & RMNET_CONV_X_SPLIT) != 0, os = (flags & RMNET_CONV_OUT_SPLIT) != 0;
+  if (!xs && !os)           // fp32 in, fp32 out: the kernel that has always served it
+    return rmnet_conv_split_f32(reinterpret_cast<const float*>(x), wpack, w_unscale, shift, res, flags, N, H, W, Cin, Cout, ksize, stride,
+                                reinterpret_cast<float*>(out), out2, out_split, range_word, stream);
+  if (!x || !wpack || !w_unscale || !out || N <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0) return RMNET_E_INVALID_ARG;
+  if (xs && (flags & RMNET_CONV_RELU_IN)) return RMNET_E_INVALID_ARG;      // (the producer of a split tensor applies it)
+  if (os && out2) return RMNET_E_INVALID_ARG;
+  if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(wpack) | reinterpret_cast<uintptr_t>(w_unscale) |
+       reinterpret_cast<uintptr_t>(shift) | reinterpret_cast<uintptr_t>(res) | reinterpret_cast<uintptr_t>(out) |
+       reinterpret_cast<uintptr_t>(out2)) & 15)
+    return RMNET_E_INVALID_ARG;
+  if (out2 && (res || out_split <= 0 || out_split >= Cout || out_split % 4)) return RMNET_E_INVALID_ARG;
+  if ((ksize != 1 && ksize != 3) || (stride != 1 && stride != 2)) return RMNET_E_UNSUPPORTED;
+  if (Cin % kKT || Cout % 64) return RMNET_E_UNSUPPORTED;
+  const int pad = ksize / 2;
+  const int Ho = (H + 2 * pad - ksize) / stride + 1, Wo = (W + 2 * pad - ksize) / stride + 1;
+  const long long Mi = (long long)N * H * W, M = (long long)N * Ho * Wo;
+  if (Mi * Cin >= (1LL << 31) || M * Cout >= (1LL << 31)) return RMNET_E_UNSUPPORTED;
+  // either form has 4 bytes per element.  No output may overlap x; an fp32 out may BE res (conv_split's rule), a split one must not
+  // overlap it: its hi and lo chunks are not where the fp32 elements of the same channels are
+  const long long xbytes = Mi * Cin * 4, c1 = out2 ? out_split : Cout;
+  if (overlap(out, M * c1 * 4, x, xbytes)) return RMNET_E_INVALID_ARG;
+  if (os && res && overlap(out, M * c1 * 4, res, M * Cout * 4)) return RMNET_E_INVALID_ARG;
+  if (out2) {
+    if (overlap(out2, M * (Cout - c1) * 4, x, xbytes) || overlap(out2, M * (Cout - c1) * 4, out, M * c1 * 4)) return RMNET_E_INVALID_ARG;
+  }
+  PreArgs a;
+  a.x = xs ? nullptr : reinterpret_cast<const float*>(x);
+  a.xs = xs ? reinterpret_cast<const _Float16*>(x) : nullptr;
+  a.wp = reinterpret_cast<const u32x4*>(wpack); a.unscale = w_unscale; a.shift = shift; a.res = res;
+  a.out = os ? nullptr : reinterpret_cast<float*>(out); a.out2 = out2; a.outs = os ? reinterpret_cast<_Float16*>(out) : nullptr;
+  a.range = range_word; a.M = (int)M; a.H = H; a.W = W; a.Ho = Ho; a.Wo = Wo; a.Cin = Cin; a.Cout = Cout; a.csplit = (int)c1;
+  a.ksize = ksize; a.stride = stride; a.pad = pad;
+  a.relu_in = (flags & RMNET_CONV_RELU_IN) != 0;
+  a.relu_out = (flags & RMNET_CONV_RELU_OUT) != 0;
+  hipStream_t st = (hipStream_t)stream;
+  if (xs && os) launch_pre_tile<true, true>(a, st);
+  else if (xs) launch_pre_tile<true, false>(a, st);
+  else launch_pre_tile<false, true>(a, st);
+  return check_launch();
+}
+
+extern "C" int rmnet_split_act_f32(const float* x, long long M, int C, int relu, void* out, int32_t* range_word, void* stream) {
+  using namespace rmnet;
+  if (!x || !out || M <= 0 || C <= 0) return RMNET_E_INVALID_ARG;
+  if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(out)) & 15) return RMNET_E_INVALID_ARG;
+  if (C % kKT) return RMNET_E_UNSUPPORTED;
+  if (M > (1LL << 40) / C) return RMNET_E_UNSUPPORTED;
+  if (overlap(out, M * C * 4, x, M * C * 4)) return RMNET_E_INVALID_ARG;      // (an item's output is not where its input was)
+  const size_t items = (size_t)M * C / 8;
+  const size_t blocks = (items + kSplitActThreads - 1) / kSplitActThreads;
+  const unsigned grid = (unsigned)(blocks < (size_t)kNumCUs * 8 ? blocks : (size_t)kNumCUs * 8);
+  hipLaunchKernelGGL(split_act, dim3(grid), dim3(kSplitActThreads), 0, (hipStream_t)stream, x, reinterpret_cast<_Float16*>(out), items,
+                     relu != 0, range_word);
   return check_launch();
 }

@@ -60,8 +60,17 @@ class _Bottleneck(nn.Module):
         if _split_path_ok(self, x, self.conv1, ('full', 'split', 'trunk')):
             x = x.contiguous(memory_format=torch.channels_last)
             rw = ops.conv_range_word(x.device)
-            t = ops.conv_split(x, self._wp1, self._wu1, self._b1, ksize=1, relu_out=True, range_word=rw)
-            t = ops.conv_split(t, self._wp2, self._wu2, self._b2, ksize=3, stride=self.conv2.stride[0], relu_out=True, range_word=rw)
+            # RMNET_CONV_PRESPLIT: t is read by exactly one later convolution each time, so it exists in split form only
+            # (include/rmnet_hip.h): split and counted once, by the epilogue that produces it, not at every tap and Cout tile of its reader
+            # The 3x3 classes gained as measured; a 1x1 reader only from PRESPLIT_MIN_CIN_1X1 input channels on (conv3 of layer3).
+            # Below that its call is two or four K steps and measured no gain (supposed, not measured: its time is in writing its
+            # output), so conv2 hands it fp32 as before
+            pre = conv_presplit()
+            # (conv1 of a stride-2 block is itself 10 % slower with a split output; with its 3x3 / stride 2 reader the pair is not:
+            #  the bench line with those two conv1 on fp32 output was the same, profiles/r17_a_presplit.md)
+            t = ops.conv_split(x, self._wp1, self._wu1, self._b1, ksize=1, relu_out=True, range_word=rw, out_presplit=pre)
+            t = ops.conv_split(t, self._wp2, self._wu2, self._b2, ksize=3, stride=self.conv2.stride[0], relu_out=True, range_word=rw,
+                               out_presplit=pre and self.conv3.in_channels >= PRESPLIT_MIN_CIN_1X1)
             if self.downsample is None:
                 return ops.conv_split(t, self._wp3, self._wu3, self._b3, res=x, ksize=1, relu_out=True, range_word=rw)
             d = ops.conv_split(x, self._wpd, self._wud, self._bd, ksize=1, stride=self.downsample[0].stride[0], range_word=rw)
@@ -293,6 +302,27 @@ def split_conv_backend():
     return v
 
 
+# Whether the trunks' bottlenecks and the key / value heads keep their convolution-to-convolution activations in split form
+# (csrc/conv_split.hip: conv_split_pre, split_act) when RMNET_CONV_PRESPLIT is not set.  The rule: on only if every bench run with
+# it is above every run without it (profiles/r17_a_presplit.md).
+PRESPLIT_DEFAULT = True
+# The fewest input channels at which a 1x1 convolution is given its input in split form.  Measured per class (one kernel trace per
+# tree, noise +-2 %): Cin 256 (Cout 1024 at 1/16) -5 %; Cin 128 (Cout 512 at 1/8) -2 % and Cin 64 (Cout 256 at 1/4) 0 %, both inside
+# the noise, so they keep their fp32 input.
+PRESPLIT_MIN_CIN_1X1 = 256
+
+
+def conv_presplit():
+    """RMNET_CONV_PRESPLIT (A/B switch, read at every call): '0' -- every split-fp16 convolution of the trunks and key / value heads
+    reads and writes fp32 (the call sequence before the split activation form existed); anything else -- a bottleneck's conv1 output,
+    and its conv2 output where conv3 gains from it (PRESPLIT_MIN_CIN_1X1), exist in split form only and KeyValue splits r4 once
+    (rmnet_split_act_f32).  Unset: PRESPLIT_DEFAULT.  Same
+    results and the same zero / non-zero range word either way."""
+    import os
+    v = os.environ.get('RMNET_CONV_PRESPLIT')
+    return PRESPLIT_DEFAULT if v is None else v.strip() != '0'
+
+
 def _split_path_ok(m, x, conv, backends):
     """Module ``m`` may run its convolutions on a split-fp16 kernel for input ``x``: fused epilogues on, packs present and allowed
     (``m._conv_split``), eval, a CUDA fp32 4-D input with ``conv``'s channels in a channels-last run (the input or the network's
@@ -366,8 +396,11 @@ class KeyValue(nn.Module):
             # both heads in ONE launch of the split-fp16 kernel over the concatenated [key | value] pack, written as two tensors
             from . import ops
             x = x.contiguous(memory_format=torch.channels_last)
-            return ops.conv_split(x, self._wp, self._wu, self._bkv, ksize=3, range_word=ops.conv_range_word(x.device),
-                                  split=self.key_conv.out_channels)
+            rw = ops.conv_range_word(x.device)
+            if conv_presplit():
+                # r4 comes from another kernel: one pass splits it (and counts), instead of 9 taps x 5 Cout tiles doing so
+                x = ops.split_act(x, range_word=rw)
+            return ops.conv_split(x, self._wp, self._wu, self._bkv, ksize=3, range_word=rw, split=self.key_conv.out_channels)
         return self.key_conv(x), self.value_conv(x)
 
 

@@ -656,21 +656,74 @@ def conv_split_pack(weight, bn_scale=None):
     return planes.contiguous().view(-1).view(torch.int16), unscale.contiguous()
 
 
+CONV_X_SPLIT, CONV_OUT_SPLIT = 4, 8  # RMNET_CONV_X_SPLIT / RMNET_CONV_OUT_SPLIT
+
+
+def is_split_act(t):
+    """``t`` is an activation in the split form of include/rmnet_hip.h: torch.float16 [N, H, W, C // 32, 2, 32], contiguous."""
+    return isinstance(t, torch.Tensor) and t.dtype == torch.float16 and t.dim() == 6 and tuple(t.shape[4:]) == (2, 32)
+
+
+def _check_split_act(t, name):
+    if not is_split_act(t):
+        raise RuntimeError('%s must be a split activation: torch.float16 [N, H, W, C // 32, 2, 32]' % name)
+    if not t.is_cuda:
+        raise RuntimeError('%s must be a CUDA tensor' % name)
+    if not t.is_contiguous():
+        raise RuntimeError('%s must be contiguous' % name)
+
+
+def split_act(x, relu=False, range_word=None):
+    """Channels-last fp32 ``x`` [N, C, H, W], C % 32 == 0 -> its split form, torch.float16 [N, H, W, C // 32, 2, 32]
+    (include/rmnet_hip.h; csrc/conv_split.hip: split_act), after a ReLU when ``relu``.  Elements outside the window are saturated
+    and counted in ``range_word`` here, once each; ``conv_split`` on the result counts nothing.  For tensors that another kernel
+    produced: ``conv_split(..., out_presplit=True)`` writes the form itself."""
+    _check_act(x, 'x')
+    if x.dim() != 4 or not x.is_contiguous(memory_format=torch.channels_last):
+        raise RuntimeError('x must be a channels-last [N, C, H, W] tensor')
+    N, C, H, W = x.shape
+    if C % 32 or x.numel() == 0:
+        raise RuntimeError('split_act needs C % 32 == 0 and a non-empty tensor, got %s' % (tuple(x.shape),))
+    if range_word is not None:
+        _check(range_word, 'range_word', torch.int32)
+        if range_word.device != x.device:
+            raise RuntimeError('split_act: every tensor must be on %s' % x.device)
+    out = torch.empty((N, H, W, C // 32, 2, 32), dtype=torch.float16, device=x.device)
+    lib = _lib.load()
+    with torch.cuda.device(x.device):
+        rc = lib.rmnet_split_act_f32(_ptr(x), N * H * W, C, 1 if relu else 0, _ptr(out), _ptr(range_word), _stream(x.device))
+    _lib.check(rc, 'rmnet_split_act_f32')
+    return out
+
+
 def conv_split(x, wpack, w_unscale, shift=None, res=None, ksize=3, stride=1, relu_in=False, relu_out=False, out=None,
-               range_word=None, split=None):
+               range_word=None, split=None, out_presplit=False):
     """act(conv(pre(x), w) + shift + res) for a channels-last fp32 ``x`` [N, Cin, H, W], kernel ``ksize`` (1 or 3, padding
     ksize // 2), ``stride`` (1 or 2) and Cout = ``w_unscale.numel()`` (a multiple of 64) on the split-fp16 MFMA kernel
     (csrc/conv_split.hip); ``pre`` / ``act`` = ReLU when ``relu_in`` / ``relu_out``.  ``wpack, w_unscale`` come from
     ``conv_split_pack``.  ``out`` (channels-last, may be ``res``, must not be ``x``) defaults to a new tensor.  ``range_word``: as
     for ``conv3x3_split``.  ``split`` (a multiple of 4 inside (0, Cout), no ``res`` / ``out``): the output channels [0, split) and
-    [split, Cout) are written to two new channels-last tensors, returned as a pair.  No fall-back: anything else is a
+    [split, Cout) are written to two new channels-last tensors, returned as a pair.
+
+    Pre-split activations (include/rmnet_hip.h): ``x`` may be a split activation (torch.float16 [N, H, W, Cin // 32, 2, 32], from
+    ``split_act`` or from ``out_presplit``); ``relu_in`` is then refused and nothing is counted for the input.  With
+    ``out_presplit`` the result is returned in that form instead of fp32 (no ``out``, no ``split``) and its elements outside the
+    window are counted in ``range_word``.  Same arithmetic and same bits either way.  No fall-back: anything else is a
     RuntimeError."""
-    _check_act(x, 'x')
-    if x.dim() != 4 or not x.is_contiguous(memory_format=torch.channels_last):
-        raise RuntimeError('x must be a channels-last [N, Cin, H, W] tensor')
+    x_split = is_split_act(x)
+    if x_split:
+        _check_split_act(x, 'x')
+        N, H, W = x.shape[:3]
+        cin = x.shape[3] * 32
+        if relu_in:
+            raise RuntimeError('conv_split: relu_in cannot be applied to a split activation (its producer applies it)')
+    else:
+        _check_act(x, 'x')
+        if x.dim() != 4 or not x.is_contiguous(memory_format=torch.channels_last):
+            raise RuntimeError('x must be a channels-last [N, Cin, H, W] tensor')
+        N, cin, H, W = x.shape
     if ksize not in (1, 3) or stride not in (1, 2):
         raise RuntimeError('conv_split implements ksize 1 / 3 and stride 1 / 2, got %r / %r' % (ksize, stride))
-    N, cin, H, W = x.shape
     _check(w_unscale, 'w_unscale')
     cout = w_unscale.numel()
     if cin % 32 or cout % 64 or cout == 0:
@@ -690,13 +743,17 @@ def conv_split(x, wpack, w_unscale, shift=None, res=None, ksize=3, stride=1, rel
         if tuple(res.shape) != shape or not res.is_contiguous(memory_format=torch.channels_last):
             raise RuntimeError('res must be a channels-last %s tensor' % (shape,))
     out2 = None
-    if split is not None:
+    if out_presplit:
+        if split is not None or out is not None:
+            raise RuntimeError('conv_split: out_presplit returns one new split activation, without split / out')
+        out = torch.empty((N, shape[2], shape[3], cout // 32, 2, 32), dtype=torch.float16, device=x.device)
+    elif split is not None:
         if res is not None or out is not None or not 0 < split < cout or split % 4:
             raise RuntimeError('conv_split: split must be a multiple of 4 in (0, %d), without res / out' % cout)
-        out = torch.empty((N, split) + shape[2:], dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
-        out2 = torch.empty((N, cout - split) + shape[2:], dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
+        out = torch.empty((N, split) + shape[2:], dtype=torch.float32, device=x.device, memory_format=torch.channels_last)
+        out2 = torch.empty((N, cout - split) + shape[2:], dtype=torch.float32, device=x.device, memory_format=torch.channels_last)
     elif out is None:
-        out = torch.empty(shape, dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
+        out = torch.empty(shape, dtype=torch.float32, device=x.device, memory_format=torch.channels_last)
     else:
         _check_act(out, 'out')
         if tuple(out.shape) != shape or not out.is_contiguous(memory_format=torch.channels_last):
@@ -709,9 +766,17 @@ def conv_split(x, wpack, w_unscale, shift=None, res=None, ksize=3, stride=1, rel
     flags = (CONV_RELU_IN if relu_in else 0) | (CONV_RELU_OUT if relu_out else 0)
     lib = _lib.load()
     with torch.cuda.device(x.device):
-        rc = lib.rmnet_conv_split_f32(_ptr(x), _ptr(wpack), _ptr(w_unscale), _ptr(shift), _ptr(res), flags, N, H, W, cin, cout,
-                                      ksize, stride, _ptr(out), _ptr(out2), split or 0, _ptr(range_word), _stream(x.device))
-    _lib.check(rc, 'rmnet_conv_split_f32')
+        if x_split or out_presplit:
+            flags |= (CONV_X_SPLIT if x_split else 0) | (CONV_OUT_SPLIT if out_presplit else 0)
+            what = 'rmnet_conv_split_pre_f32'
+            rc = lib.rmnet_conv_split_pre_f32(_ptr(x), _ptr(wpack), _ptr(w_unscale), _ptr(shift), _ptr(res), flags, N, H, W, cin,
+                                              cout, ksize, stride, _ptr(out), _ptr(out2), split or 0, _ptr(range_word),
+                                              _stream(x.device))
+        else:
+            what = 'rmnet_conv_split_f32'
+            rc = lib.rmnet_conv_split_f32(_ptr(x), _ptr(wpack), _ptr(w_unscale), _ptr(shift), _ptr(res), flags, N, H, W, cin, cout,
+                                          ksize, stride, _ptr(out), _ptr(out2), split or 0, _ptr(range_word), _stream(x.device))
+    _lib.check(rc, what)
     return out if out2 is None else (out, out2)
 
 
