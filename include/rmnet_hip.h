@@ -106,6 +106,8 @@ int rmnet_boxes_to_cell_rects_i32(const int32_t *bboxes, int n_boxes, int k_per_
  *   flags  RMNET_MR_* below.
  * The fast path needs De == 128 and Do == 512 (RMNet's sizes, models/rmnet.py:185-186); other
  * sizes run a generic (slow, still on-GPU) path that needs the p-sized workspace.
+ * Generic path: De <= 224 (RMNET_E_UNSUPPORTED beyond: its query tile lives in 64 KB of LDS), any Do; the same limit
+ * holds for p_out at the fast shape, which that path computes.  Rectangles may stick out of the grid or be empty.
  * Fast path arithmetic: the memory is first staged (one launch, inside `workspace`) into a transient
  * split-fp16 bank (below) and read with 3-term fp16 MFMAs, fp32 accumulate -- fp32-class accuracy for
  * |K|, |V| < 1023.5.  The staging pass counts elements outside that window on the device; if there is

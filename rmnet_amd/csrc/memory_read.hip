@@ -631,9 +631,11 @@ __global__ __launch_bounds__(kThreads, kCombCh == 16 ? 6 : 5) void mr_combine(co
 }
 
 // ------------------------------------------------------------------------------------------
-// Generic path (any De <= 256, any Do) and the optional p output: a plain three-pass soft-max
+// Generic path (any De <= 224, any Do) and the optional p output: a plain three-pass soft-max
 // that materialises p, then a plain V p product.  Correct for every shape, not tuned: RMNet only
-// ever uses De = 128 / Do = 512 and never reads p (models/rmnet.py:361-366).
+// ever uses De = 128 / Do = 512 and never reads p (models/rmnet.py:361-366).  De <= 224: p_kernel's
+// query tile [De][64] and its 256 reduction words share 64 KB of dynamic LDS (launch_memory_read
+// returns RMNET_E_UNSUPPORTED beyond; include/rmnet_hip.h states the same limit).
 // ------------------------------------------------------------------------------------------
 struct GArgs {
   const float *mk, *mv, *qk, *qv;
