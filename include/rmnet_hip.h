@@ -294,6 +294,14 @@ int rmnet_affine_relu_maxpool_nhwc_f32(const float *x, const float *scale, const
 int rmnet_conv3x3_split_f32(const float *x, const void *wpack, const float *w_unscale, const float *bias, const float *res, int flags,
                             int N, int H, int W, int Cin, float *out, int32_t *range_word, void *stream);
 
+/* The same convolution on the kernel that stages the weights through LDS (additive export, same ABI version): the arguments,
+ * argument rules and return codes of rmnet_conv3x3_split_f32, and its results bit for bit, range word included.
+ * rmnet_conv3x3_split_f32 runs conv3x3_wreg, whose waves load their weight fragments straight from the pack into registers;
+ * this entry runs conv3x3_split, the kernel that entry ran before, and is kept for A/B measurements and as the reference of
+ * tests/test_conv3x3_wreg.py (rmnet_amd.ops.conv3x3_split selects it with RMNET_CONV3X3_KERNEL=lds). */
+int rmnet_conv3x3_split_lds_f32(const float *x, const void *wpack, const float *w_unscale, const float *bias, const float *res,
+                                int flags, int N, int H, int W, int Cin, float *out, int32_t *range_word, void *stream);
+
 /* C1 trunk / key-value convolutions (additive export, same ABI version): the arithmetic, range word and flags of
  * rmnet_conv3x3_split_f32 for kernel size ksize = 1 or 3 (padding ksize / 2), stride 1 or 2 and Cout % 64 == 0 (csrc/conv_split.hip).
  * Replaces the ResNet-50 bottleneck convolutions (BatchNorm folded into the pack, skip add and ReLU in the epilogue) and the two

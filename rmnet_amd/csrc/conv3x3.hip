@@ -43,6 +43,19 @@
 //                  that needs them (with / without ReLU x centre tap or not) instead of being tested per element.
 // Ceiling at the 1/4-resolution shape (M = 414720, Cin = 256): 3240 workgroups, 72 steps each,
 // 1536 clk/step -> ~13 rounds x 110 k clk / 2.4 GHz ~ 0.6 ms (= the 2.5 PF fp16 roof / 3).
+//
+// Two kernels.  All of the above is conv3x3_split, which rmnet_conv3x3_split_lds_f32 launches.  rmnet_conv3x3_split_f32 launches
+// conv3x3_wreg (below conv3x3_split in this file): the same pixels, channels, arithmetic and K order, but the weights do not pass
+// through LDS.  A weight fragment is used by two waves only in conv3x3_split's layout, and by one in conv3x3_wreg's, so each lane
+// loads its own 16 bytes of it from the pack.  Per K step and workgroup, conv3x3_wreg:
+//   global reads   as above: activations 16 KB, weights 32 KB (each byte by exactly one wave, in whole 1 KB fragments)
+//   LDS            X hi/lo [128][32] fp16 = 16 KB per buffer, two buffers = 32768 B (= 2 * 2 * 128 * 32 * 2; tests/test_conv3x3_wreg.py)
+//   LDS writes     16 KB (the next step's X tile); no weight writes (32 ds_write_b128 wave-instructions per step gone)
+//   LDS reads      per wave 8 pixel tiles x hi/lo x 1 KB = 16 KB, per CU 128 KB as above, but all of it X; each tile's two reads are
+//                  issued one tile (six MFMAs) ahead of their use
+//   registers      weights 2 sets x 4 fragments x 4 VGPRs (this step's, the next step's), activations' prefetch 8, X fragments 16
+//   MFMA           per wave 8 x 2 tiles x 3 terms = 48, the same 1536 clk per step and SIMD; the ceiling above is unchanged.
+// Measured (profiles/r19_a_conv3x3_wreg.md): 4-7 % less time per call than conv3x3_split, the same bits.
 #include "common.h"
 
 namespace rmnet {
@@ -327,13 +340,247 @@ __global__ __launch_bounds__(kThreads) void conv3x3_split(ConvArgs a) {
   if (a.range && bad) atomicAdd(a.range, bad);
 }
 
+
+// ---------------------------------------------------------------------------------------------------------------- conv3x3_wreg
+// The same convolution with the weights kept out of LDS (the banner's last part).  Arguments, arithmetic, K order per accumulator
+// and epilogue expressions are conv3x3_split's, so outputs and range words are bit for bit the same; what differs is who owns what:
+//   waves        the 8 waves divide the 256 output channels: wave w owns all 128 pixels x channels 32w .. 32w+31 = 8 x 2 MFMA tiles
+//                (still 48 MFMAs per wave and step, still 2 x 64 accumulator VGPRs).  No two waves need the same weight fragment.
+//   weights      the A fragment of one MFMA tile (16 channels x 32 of K of one plane) is 1 KB of contiguous pack memory, and lane
+//                (fr, fc) owns the 16 bytes at fr*64 + fc*16: one 16-byte load per lane and fragment, four per step (2 channel
+//                tiles x hi / lo), straight into the VGPRs the next step's MFMAs read.  Two register sets take turns (the step
+//                loop runs in pairs), so nothing is copied except once per tap when the tap's step count is odd.
+//   activations  as in conv3x3_split: fp32 loads, tap mask, the split between the MFMAs of the step's second half, swizzled X
+//                planes.  Every wave reads all eight pixel tiles' hi / lo fragments (16 KB per wave and step, what a wave of
+//                conv3x3_split reads), each tile's two reads one tile ahead of the six MFMAs that use it.
+//   LDS          X only: 2 buffers x 2 planes x [128][32] fp16 = 32768 B.
+constexpr int kXBufHalves = 2 * kXPlane;
+
+__global__ __launch_bounds__(kThreads) void conv3x3_wreg(ConvArgs a) {
+  __shared__ __attribute__((aligned(16))) _Float16 lds[2 * kXBufHalves];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int fr = lane & 15, fc = lane >> 4;
+  const int m0 = blockIdx.x * kMT;
+  const int HW = a.H * a.W, CB = a.Cin / kKT;
+
+  // activation loader: conv3x3_split's (pixel p = tid/8 + 64i, channels 4*(tid&7) ..)
+  const int c4 = tid & 7;
+  int pm[2];
+  unsigned inside[2];
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    const int m = m0 + (tid >> 3) + 64 * i;
+    const bool pin = m < a.M;
+    pm[i] = pin ? m : 0;
+    const int r = pm[i] % HW;
+    const int ph = r / a.W, pw = r % a.W;
+    inside[i] = 0;
+#pragma unroll
+    for (int t = 0; t < 9; ++t) {
+      const int h = ph + t / 3 - 1, w = pw + t % 3 - 1;
+      inside[i] |= (pin && h >= 0 && h < a.H && w >= 0 && w < a.W ? 1u : 0u) << t;
+    }
+  }
+  f32x4 xr[2];
+  int bad = 0;
+  const float* xb = a.x;
+  unsigned xo[2];
+  bool in[2];
+  auto set_tap = [&](int tap) {
+    const int d = (tap / 3 - 1) * a.W + (tap % 3 - 1);
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      in[i] = (inside[i] >> tap) & 1;
+      xo[i] = (unsigned)(pm[i] + (in[i] ? d : 0)) * a.Cin + 4 * c4;
+    }
+    xb = a.x;
+  };
+  auto load_x = [&] {
+#pragma unroll
+    for (int i = 0; i < 2; ++i) xr[i] = *reinterpret_cast<const f32x4*>(xb + xo[i]);
+    xb += kKT;
+  };
+  // weight fragments [2 * channel tile + plane]: 16-byte chunk plane*1024 + co*4 + fc of the step's 2048, co = 32*wave + 16*j + fr
+  half8 wa[4], wb[4];
+  const half8* wsrc = a.wp;                                  // the step's pack (uniform)
+  const unsigned wl = (wave * 32 + fr) * 4 + fc;             // the lane's chunk of channel tile 0, plane hi
+  auto load_w = [&](half8(&w)[4]) __attribute__((always_inline)) {
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+#pragma unroll
+      for (int p = 0; p < 2; ++p) w[2 * j + p] = wsrc[wl + (unsigned)(p * (kWPlane / 8) + j * 64)];
+    wsrc += 2 * kWPlane / 8;
+  };
+  auto store_x = [&](auto relu, auto centre, _Float16* buf) __attribute__((always_inline)) {
+    _Float16* xh = buf;
+    _Float16* xl = buf + kXPlane;
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      half4 hi, lo;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        float v = in[i] ? xr[i][e] : 0.0f;
+        if constexpr (decltype(relu)::value) v = v < 0.0f ? 0.0f : v;          // (keeps NaN: it is counted below)
+        const float y = v * kActScale;
+        if constexpr (decltype(centre)::value) bad += !(fabsf(y) <= kF16Max) ? 1 : 0;
+        const float c = fminf(fmaxf(y, -kF16Max), kF16Max);   // NaN -> -65504 (saturated, counted)
+        const _Float16 h = (_Float16)c;
+        hi[e] = h;
+        lo[e] = (_Float16)(c - (float)h);
+      }
+      const int p = (tid >> 3) + 64 * i;
+      const int o = swz(p, c4 >> 1) + 4 * (c4 & 1);
+      *reinterpret_cast<half4*>(xh + o) = hi;
+      *reinterpret_cast<half4*>(xl + o) = lo;
+    }
+  };
+
+  // acc[pixel tile][channel tile]: hi*hi, and the two cross terms, as in conv3x3_split
+  f32x4 acc[8][2], accx[8][2];
+#pragma unroll
+  for (int i = 0; i < 8; ++i)
+#pragma unroll
+    for (int j = 0; j < 2; ++j) acc[i][j] = accx[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+  set_tap(0);
+  load_x();
+  load_w(wa);
+  if (a.relu_in)
+    store_x(Flag<true>{}, Flag<false>{}, lds);
+  else
+    store_x(Flag<false>{}, Flag<false>{}, lds);
+  __syncthreads();
+  // One pixel tile at a time: its hi / lo fragments, then its six MFMAs -- per accumulator Ah*Bh, then Ah*Bl, then Al*Bh, which is
+  // conv3x3_split's order.  (The swizzle term of a fragment's address depends on fr alone: the eight tiles are 1 KB apart.)
+  auto mma = [&](const _Float16* __restrict__ cur, const half8(&w)[4], auto&& halfway) __attribute__((always_inline)) {
+    const _Float16* xh = cur + swz(fr, fc);
+    const _Float16* xl = xh + kXPlane;
+    half8 bh[2], bl[2];       // tile i + 1's fragments are read in front of tile i's MFMAs
+    bh[0] = *reinterpret_cast<const half8*>(xh);
+    bl[0] = *reinterpret_cast<const half8*>(xl);
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      if (i + 1 < 8) {
+        bh[(i + 1) & 1] = *reinterpret_cast<const half8*>(xh + (i + 1) * 16 * kKT);
+        bl[(i + 1) & 1] = *reinterpret_cast<const half8*>(xl + (i + 1) * 16 * kKT);
+      }
+      const half8 h = bh[i & 1], l = bl[i & 1];
+#pragma unroll
+      for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(w[2 * j], h, acc[i][j], 0, 0, 0);
+#pragma unroll
+      for (int j = 0; j < 2; ++j) accx[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(w[2 * j], l, accx[i][j], 0, 0, 0);
+#pragma unroll
+      for (int j = 0; j < 2; ++j) accx[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(w[2 * j + 1], h, accx[i][j], 0, 0, 0);
+      if (i == 3) halfway();
+    }
+  };
+  // A step: all six loads of the next step first (the weights into the register set this step does not read), the MFMAs of this
+  // one, the next step's activation split between the MFMAs of the second half (conv3x3_split's fences and groups), the barrier.
+  // The weight loads stay in flight across the barrier: their first readers are the next step's MFMAs.
+  int par = 0;
+  auto step = [&](auto relu, auto centre, const half8(&wc)[4], half8(&wn)[4]) __attribute__((always_inline)) {
+    _Float16* nxt = lds + (par ^ 1) * kXBufHalves;
+    load_x();
+    __builtin_amdgcn_sched_barrier(0);     // (activations first: the split half way waits for them alone, by count)
+    load_w(wn);
+    __builtin_amdgcn_sched_barrier(0);
+    mma(lds + par * kXBufHalves, wc, [&] {
+      __builtin_amdgcn_sched_barrier(0);
+      store_x(relu, centre, nxt);
+    });
+#pragma unroll
+    for (int g = 0; g < 24; ++g) {
+      if (g % 6 == 0 && g < 18) __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);     // the next tile's two fragment reads
+      __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);     // one MFMA,
+      __builtin_amdgcn_sched_group_barrier(0x002, 3, 0);     // three VALU instructions of the split
+    }
+    __builtin_amdgcn_sched_barrier(0);
+    __syncthreads();
+    par ^= 1;
+  };
+  auto run_taps = [&](auto relu, auto centre, int t0, int t1) __attribute__((always_inline)) {
+#pragma unroll 1
+    for (int tap = t0; tap < t1; ++tap) {
+      if (tap) set_tap(tap);
+      const int n = tap ? CB : CB - 1;       // (tap 0's first block was the prologue's)
+      int k = 0;
+#pragma unroll 1
+      for (; k + 1 < n; k += 2) {            // in pairs: the two weight sets change roles, no copy
+        step(relu, centre, wa, wb);
+        step(relu, centre, wb, wa);
+      }
+      if (k < n) {                           // an odd count: one more step, and the sets change names
+        step(relu, centre, wa, wb);
+#pragma unroll
+        for (int f = 0; f < 4; ++f) wa[f] = wb[f];
+      }
+    }
+  };
+  auto run = [&](auto relu) __attribute__((always_inline)) {
+    run_taps(relu, Flag<false>{}, 0, 4);
+    run_taps(relu, Flag<true>{}, 4, 5);
+    run_taps(relu, Flag<false>{}, 5, 9);
+  };
+  if (a.relu_in)
+    run(Flag<true>{});
+  else
+    run(Flag<false>{});
+  mma(lds + par * kXBufHalves, wa, [] {});
+
+  // epilogue: conv3x3_split's, with pixel m0 + 16i + fr and channels 32*wave + 16j + 4*fc ..
+  f32x4 r[8][2];
+  if (a.res) {
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      const int m = m0 + i * 16 + fr;
+#pragma unroll
+      for (int j = 0; j < 2; ++j) {
+        const int co = wave * 32 + j * 16 + 4 * fc;
+        r[i][j] = m < a.M ? *reinterpret_cast<const f32x4*>(a.res + (size_t)m * kCout + co) : f32x4{0.f, 0.f, 0.f, 0.f};
+      }
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < 2; ++j) {
+    const int co = wave * 32 + j * 16 + 4 * fc;
+    const f32x4 us = *reinterpret_cast<const f32x4*>(a.w_unscale + co) * kActUnscale;
+    const f32x4 b = a.bias ? *reinterpret_cast<const f32x4*>(a.bias + co) : f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int i = 0; i < 8; ++i) acc[i][j] = (acc[i][j] + accx[i][j]) * us + b;
+  }
+#pragma unroll
+  for (int j = 0; j < 2; ++j)
+#pragma unroll
+    for (int i = 0; i < 8; ++i) asm volatile("" : "+v"(acc[i][j]));
+#pragma unroll
+  for (int j = 0; j < 2; ++j) {
+    const int co = wave * 32 + j * 16 + 4 * fc;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      const int m = m0 + i * 16 + fr;
+      if (m >= a.M) continue;
+      const size_t off = (size_t)m * kCout + co;
+      f32x4 v = acc[i][j];
+      if (a.res) v += r[i][j];
+      if (a.relu_out) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) v[e] = v[e] < 0.0f ? 0.0f : v[e];
+      }
+      *reinterpret_cast<f32x4*>(a.out + off) = v;
+    }
+  }
+  if (a.range && bad) atomicAdd(a.range, bad);
+}
+
 }  // namespace
 }  // namespace rmnet
 
-extern "C" int rmnet_conv3x3_split_f32(const float* x, const void* wpack, const float* w_unscale, const float* bias,
-                                       const float* res, int flags, int N, int H, int W, int Cin, float* out,
-                                       int32_t* range_word, void* stream) {
-  using namespace rmnet;
+namespace rmnet {
+namespace {
+
+// both entries: the same argument rules, one kernel each
+int conv3x3_launch(void (*kernel)(ConvArgs), const float* x, const void* wpack, const float* w_unscale, const float* bias,
+                   const float* res, int flags, int N, int H, int W, int Cin, float* out, int32_t* range_word, void* stream) {
   if (!x || !wpack || !w_unscale || !out || N <= 0 || H <= 0 || W <= 0 || Cin <= 0) return RMNET_E_INVALID_ARG;
   if (flags & ~(RMNET_CONV_RELU_IN | RMNET_CONV_RELU_OUT)) return RMNET_E_INVALID_ARG;
   if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(wpack) | reinterpret_cast<uintptr_t>(w_unscale) |
@@ -353,6 +600,21 @@ extern "C" int rmnet_conv3x3_split_f32(const float* x, const void* wpack, const 
   a.range = range_word; a.M = (int)M; a.H = H; a.W = W; a.Cin = Cin;
   a.relu_in = (flags & RMNET_CONV_RELU_IN) != 0;
   a.relu_out = (flags & RMNET_CONV_RELU_OUT) != 0;
-  hipLaunchKernelGGL(conv3x3_split, dim3((unsigned)((M + kMT - 1) / kMT)), dim3(kThreads), 0, (hipStream_t)stream, a);
+  hipLaunchKernelGGL(kernel, dim3((unsigned)((M + kMT - 1) / kMT)), dim3(kThreads), 0, (hipStream_t)stream, a);
   return check_launch();
+}
+
+}  // namespace
+}  // namespace rmnet
+
+extern "C" int rmnet_conv3x3_split_f32(const float* x, const void* wpack, const float* w_unscale, const float* bias,
+                                       const float* res, int flags, int N, int H, int W, int Cin, float* out,
+                                       int32_t* range_word, void* stream) {
+  return rmnet::conv3x3_launch(rmnet::conv3x3_wreg, x, wpack, w_unscale, bias, res, flags, N, H, W, Cin, out, range_word, stream);
+}
+
+extern "C" int rmnet_conv3x3_split_lds_f32(const float* x, const void* wpack, const float* w_unscale, const float* bias,
+                                           const float* res, int flags, int N, int H, int W, int Cin, float* out,
+                                           int32_t* range_word, void* stream) {
+  return rmnet::conv3x3_launch(rmnet::conv3x3_split, x, wpack, w_unscale, bias, res, flags, N, H, W, Cin, out, range_word, stream);
 }

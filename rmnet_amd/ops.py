@@ -8,6 +8,7 @@ RuntimeError) and additionally checks dtype, which the reference only assumes.
 """
 
 import ctypes
+import os
 
 import numpy as np
 import torch
@@ -578,6 +579,24 @@ def conv_range_word(device):
     return w
 
 
+# The kernel behind conv3x3_split when RMNET_CONV3X3_KERNEL is not set: 'wreg' -- conv3x3_wreg, weight fragments loaded straight
+# into registers (rmnet_conv3x3_split_f32); 'lds' -- conv3x3_split, weights staged through LDS (rmnet_conv3x3_split_lds_f32).
+# Both return the same bits.  The rule: 'wreg' only if every bench run with it is above every run with 'lds'
+# (profiles/r19_a_conv3x3_wreg.md).
+CONV3X3_KERNEL_DEFAULT = 'wreg'
+CONV3X3_ENTRIES = {'wreg': 'rmnet_conv3x3_split_f32', 'lds': 'rmnet_conv3x3_split_lds_f32'}
+
+
+def conv3x3_entry():
+    """The export that ``conv3x3_split`` calls: RMNET_CONV3X3_KERNEL ('wreg' or 'lds', read at every call; unset:
+    CONV3X3_KERNEL_DEFAULT).  Any other value is a RuntimeError."""
+    v = os.environ.get('RMNET_CONV3X3_KERNEL')
+    v = CONV3X3_KERNEL_DEFAULT if v is None else v.strip()
+    if v not in CONV3X3_ENTRIES:
+        raise RuntimeError('RMNET_CONV3X3_KERNEL must be one of %s, got %r' % (sorted(CONV3X3_ENTRIES), v))
+    return CONV3X3_ENTRIES[v]
+
+
 def conv3x3_split(x, wpack, w_unscale, bias=None, res=None, relu_in=False, relu_out=False, out=None, range_word=None):
     """act(conv3x3(pre(x), w) + bias + res) for a channels-last fp32 ``x`` [N, Cin, H, W] and 256 output channels, stride 1,
     padding 1, on the split-fp16 MFMA kernel (csrc/conv3x3.hip); ``pre`` / ``act`` = ReLU when ``relu_in`` / ``relu_out``.
@@ -618,11 +637,12 @@ def conv3x3_split(x, wpack, w_unscale, bias=None, res=None, relu_in=False, relu_
         if t is not None and t.device != x.device:
             raise RuntimeError('conv3x3_split: every tensor must be on %s' % x.device)
     flags = (CONV_RELU_IN if relu_in else 0) | (CONV_RELU_OUT if relu_out else 0)
+    entry = conv3x3_entry()
     lib = _lib.load()
     with torch.cuda.device(x.device):
-        rc = lib.rmnet_conv3x3_split_f32(_ptr(x), _ptr(wpack), _ptr(w_unscale), _ptr(bias), _ptr(res), flags, N, H, W, cin,
-                                         _ptr(out), _ptr(range_word), _stream(x.device))
-    _lib.check(rc, 'rmnet_conv3x3_split_f32')
+        rc = getattr(lib, entry)(_ptr(x), _ptr(wpack), _ptr(w_unscale), _ptr(bias), _ptr(res), flags, N, H, W, cin,
+                                 _ptr(out), _ptr(range_word), _stream(x.device))
+    _lib.check(rc, entry)
     return out
 
 
