@@ -302,6 +302,17 @@ int rmnet_conv3x3_split_f32(const float *x, const void *wpack, const float *w_un
 int rmnet_conv3x3_split_lds_f32(const float *x, const void *wpack, const float *w_unscale, const float *bias, const float *res,
                                 int flags, int N, int H, int W, int Cin, float *out, int32_t *range_word, void *stream);
 
+/* The same convolution for Cin = 256 on the kernel that stages a whole tap row of activations in LDS once (additive export, same
+ * ABI version; csrc/conv3x3_rows.hip: conv3x3_rows): the arguments, argument rules and return codes of rmnet_conv3x3_split_f32, and
+ * its results bit for bit, range word included -- the K order per accumulator, the operand bits and the epilogue are the same.
+ * Additionally RMNET_E_UNSUPPORTED unless Cin == 256 (the row image, 130 pixels x 256 channels x hi / lo, is what fits a CU's
+ * LDS), and nothing is written then.  The kernel asks for 137216 B of dynamic LDS, which needs a function attribute: it is set at
+ * the first call on a device, and that first call must not come from a stream that is capturing (RMNET_E_UNSUPPORTED): call once
+ * eagerly before capturing.  rmnet_amd.ops.conv3x3_split selects this entry with RMNET_CONV3X3_ROWS when RMNET_CONV3X3_KERNEL is
+ * not set. */
+int rmnet_conv3x3_rows_f32(const float *x, const void *wpack, const float *w_unscale, const float *bias, const float *res, int flags,
+                           int N, int H, int W, int Cin, float *out, int32_t *range_word, void *stream);
+
 /* C1 trunk / key-value convolutions (additive export, same ABI version): the arithmetic, range word and flags of
  * rmnet_conv3x3_split_f32 for kernel size ksize = 1 or 3 (padding ksize / 2), stride 1 or 2 and Cout % 64 == 0 (csrc/conv_split.hip).
  * Replaces the ResNet-50 bottleneck convolutions (BatchNorm folded into the pack, skip add and ReLU in the epilogue) and the two

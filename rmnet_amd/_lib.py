@@ -86,6 +86,9 @@ SIGNATURES = {
     'rmnet_conv3x3_split_lds_f32': (ctypes.c_int, [
         c_f32p, ctypes.c_void_p, c_f32p, c_f32p, c_f32p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
         c_f32p, c_i32p, ctypes.c_void_p]),
+    'rmnet_conv3x3_rows_f32': (ctypes.c_int, [
+        c_f32p, ctypes.c_void_p, c_f32p, c_f32p, c_f32p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+        c_f32p, c_i32p, ctypes.c_void_p]),
     'rmnet_conv_split_f32': (ctypes.c_int, [
         c_f32p, ctypes.c_void_p, c_f32p, c_f32p, c_f32p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
         ctypes.c_int, ctypes.c_int, ctypes.c_int, c_f32p, c_f32p, ctypes.c_int, c_i32p, ctypes.c_void_p]),

@@ -597,6 +597,24 @@ def conv3x3_entry():
     return CONV3X3_ENTRIES[v]
 
 
+# The Cin = 256 convolutions on conv3x3_rows (csrc/conv3x3_rows.hip: a tap row's activations staged in LDS once; the same bits)
+# when RMNET_CONV3X3_ROWS is not set.  The rule: True only if every bench run with it is above every run of the parent commit and
+# above every run of the same tree with the switch off (profiles/r20_a_conv3x3_rows.md).
+CONV3X3_ROWS_DEFAULT = True
+CONV3X3_ROWS_ENTRY = 'rmnet_conv3x3_rows_f32'
+CONV3X3_ROWS_CIN = 256
+
+
+def conv3x3_rows_enabled():
+    """RMNET_CONV3X3_ROWS ('0' or '1', read at every call; unset: CONV3X3_ROWS_DEFAULT).  Any other value is a RuntimeError."""
+    v = os.environ.get('RMNET_CONV3X3_ROWS')
+    if v is None:
+        return CONV3X3_ROWS_DEFAULT
+    if v.strip() not in ('0', '1'):
+        raise RuntimeError("RMNET_CONV3X3_ROWS must be '0' or '1', got %r" % v)
+    return v.strip() == '1'
+
+
 def conv3x3_split(x, wpack, w_unscale, bias=None, res=None, relu_in=False, relu_out=False, out=None, range_word=None):
     """act(conv3x3(pre(x), w) + bias + res) for a channels-last fp32 ``x`` [N, Cin, H, W] and 256 output channels, stride 1,
     padding 1, on the split-fp16 MFMA kernel (csrc/conv3x3.hip); ``pre`` / ``act`` = ReLU when ``relu_in`` / ``relu_out``.
@@ -638,6 +656,9 @@ def conv3x3_split(x, wpack, w_unscale, bias=None, res=None, relu_in=False, relu_
             raise RuntimeError('conv3x3_split: every tensor must be on %s' % x.device)
     flags = (CONV_RELU_IN if relu_in else 0) | (CONV_RELU_OUT if relu_out else 0)
     entry = conv3x3_entry()
+    # conv3x3_rows: the switch on, no kernel named explicitly (RMNET_CONV3X3_KERNEL=wreg|lds always gets that kernel), Cin = 256
+    if conv3x3_rows_enabled() and os.environ.get('RMNET_CONV3X3_KERNEL') is None and cin == CONV3X3_ROWS_CIN:
+        entry = CONV3X3_ROWS_ENTRY
     lib = _lib.load()
     with torch.cuda.device(x.device):
         rc = getattr(lib, entry)(_ptr(x), _ptr(wpack), _ptr(w_unscale), _ptr(bias), _ptr(res), flags, N, H, W, cin,
