@@ -365,6 +365,20 @@ int rmnet_conv_split_pre_f32(const void *x, const void *wpack, const float *w_un
                              int32_t *range_word, void *stream);
 int rmnet_split_act_f32(const float *x, long long M, int C, int relu, void *out, int32_t *range_word, void *stream);
 
+/* The trunks' stride-1 3x3 bottleneck convolutions on the kernel that stages a whole tap row of activations in LDS once (additive
+ * export, same ABI version; csrc/conv_rows.hip: conv_rows<C>): the arguments and argument rules of rmnet_conv_split_pre_f32, and its
+ * results bit for bit, range word included -- the K order per accumulator, the operand bits and the epilogue are the same -- for
+ *   ksize = 3, stride = 1, Cin == Cout in {64, 128, 256}, RMNET_CONV_X_SPLIT set (x in split form), out fp32 or, with
+ *   RMNET_CONV_OUT_SPLIT, in split form, shift optional, RMNET_CONV_RELU_OUT optional, res == NULL and out2 == NULL.
+ * Every other call that rmnet_conv_split_pre_f32 would accept returns RMNET_E_UNSUPPORTED and writes nothing.  A workgroup owns
+ * 32768 / C consecutive pixels and all C channels; the kernel asks for up to 137216 B of dynamic LDS, which needs a function
+ * attribute: it is set at the first call of an instance (C, output form) on a device, and that first call must not come from a
+ * stream that is capturing (RMNET_E_UNSUPPORTED): call once eagerly before capturing.  rmnet_amd.ops.conv_split selects this entry
+ * with RMNET_TRUNK_ROWS for the classes of ops.TRUNK_ROWS_CLASSES. */
+int rmnet_conv_rows_pre_f32(const void *x, const void *wpack, const float *w_unscale, const float *shift, const float *res, int flags,
+                            int N, int H, int W, int Cin, int Cout, int ksize, int stride, void *out, float *out2, int out_split,
+                            int32_t *range_word, void *stream);
+
 /* C1 encoder stems (additive export, same ABI version): the 7x7 / stride 2 / pad 3 stem convolution, the folded BatchNorm, ReLU and
  * MaxPool2d(3, stride 2, padding 1) in ONE launch (csrc/stem.hip), on the split-fp16 arithmetic of rmnet_conv3x3_split_f32; the
  * half-resolution 64-channel activation is never written.  Replaces conv1 (+ conv1_m + conv1_o) / bn1 / relu / maxpool of both

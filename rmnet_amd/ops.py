@@ -737,6 +737,28 @@ def split_act(x, relu=False, range_word=None):
     return out
 
 
+# The trunks' stride-1 3x3 bottleneck convolutions (split input, Cin == Cout, no residual) on conv_rows (csrc/conv_rows.hip: a tap
+# row's activations staged in LDS once; the same bits) when RMNET_TRUNK_ROWS is not set, for the channel counts of
+# TRUNK_ROWS_CLASSES.  The rules (profiles/r21_a_trunk_rows.md): the default is True only if every bench run with it is above every
+# run of the parent commit; a class is listed only if its per-call time in a kernel trace falls by more than the classes whose code
+# did not change move.  TRUNK_ROWS_ALL is what the export implements; the 64-channel class (layer1, 1/4 maps) measured the same
+# time on either kernel (-1.0 % in the trace, inside the -0.2 to +1.3 % of the unchanged classes) and stays on conv_split_pre.
+TRUNK_ROWS_DEFAULT = True
+TRUNK_ROWS_ENTRY = 'rmnet_conv_rows_pre_f32'
+TRUNK_ROWS_ALL = (64, 128, 256)
+TRUNK_ROWS_CLASSES = (128, 256)
+
+
+def trunk_rows_enabled():
+    """RMNET_TRUNK_ROWS ('0' or '1', read at every call; unset: TRUNK_ROWS_DEFAULT).  Any other value is a RuntimeError."""
+    v = os.environ.get('RMNET_TRUNK_ROWS')
+    if v is None:
+        return TRUNK_ROWS_DEFAULT
+    if v.strip() not in ('0', '1'):
+        raise RuntimeError("RMNET_TRUNK_ROWS must be '0' or '1', got %r" % v)
+    return v.strip() == '1'
+
+
 def conv_split(x, wpack, w_unscale, shift=None, res=None, ksize=3, stride=1, relu_in=False, relu_out=False, out=None,
                range_word=None, split=None, out_presplit=False):
     """act(conv(pre(x), w) + shift + res) for a channels-last fp32 ``x`` [N, Cin, H, W], kernel ``ksize`` (1 or 3, padding
@@ -805,14 +827,17 @@ def conv_split(x, wpack, w_unscale, shift=None, res=None, ksize=3, stride=1, rel
         if t is not None and t.device != x.device:
             raise RuntimeError('conv_split: every tensor must be on %s' % x.device)
     flags = (CONV_RELU_IN if relu_in else 0) | (CONV_RELU_OUT if relu_out else 0)
+    # conv_rows: the switch on (read at every call, so a bad value raises whatever the shape), and the class it serves
+    rows = trunk_rows_enabled() and x_split and ksize == 3 and stride == 1 and cin == cout and cin in TRUNK_ROWS_CLASSES \
+        and res is None and split is None
     lib = _lib.load()
     with torch.cuda.device(x.device):
         if x_split or out_presplit:
             flags |= (CONV_X_SPLIT if x_split else 0) | (CONV_OUT_SPLIT if out_presplit else 0)
-            what = 'rmnet_conv_split_pre_f32'
-            rc = lib.rmnet_conv_split_pre_f32(_ptr(x), _ptr(wpack), _ptr(w_unscale), _ptr(shift), _ptr(res), flags, N, H, W, cin,
-                                              cout, ksize, stride, _ptr(out), _ptr(out2), split or 0, _ptr(range_word),
-                                              _stream(x.device))
+            what = TRUNK_ROWS_ENTRY if rows else 'rmnet_conv_split_pre_f32'
+            rc = getattr(lib, what)(_ptr(x), _ptr(wpack), _ptr(w_unscale), _ptr(shift), _ptr(res), flags, N, H, W, cin,
+                                    cout, ksize, stride, _ptr(out), _ptr(out2), split or 0, _ptr(range_word),
+                                    _stream(x.device))
         else:
             what = 'rmnet_conv_split_f32'
             rc = lib.rmnet_conv_split_f32(_ptr(x), _ptr(wpack), _ptr(w_unscale), _ptr(shift), _ptr(res), flags, N, H, W, cin, cout,
