@@ -21,14 +21,17 @@ def hipcc_path():
     raise RuntimeError('hipcc not found: librmnet_hip.so cannot be built')
 
 
+def dependencies():
+    """Every file whose edit must rebuild the library: the sources, every header of csrc/ and the C ABI's header."""
+    headers = sorted(f for f in os.listdir(CSRC) if f.endswith('.h'))
+    return [os.path.join(CSRC, f) for f in SOURCES + headers] + [os.path.join(os.path.dirname(HERE), 'include', 'rmnet_hip.h')]
+
+
 def needs_build():
     if not os.path.exists(LIB):
         return True
     t = os.path.getmtime(LIB)
-    deps = [os.path.join(CSRC, s) for s in SOURCES] + [
-        os.path.join(CSRC, 'common.h'),
-        os.path.join(os.path.dirname(HERE), 'include', 'rmnet_hip.h')]
-    return any(os.path.getmtime(d) > t for d in deps)
+    return any(os.path.getmtime(d) > t for d in dependencies())
 
 
 def build_library(force=False, verbose=False):

@@ -27,21 +27,10 @@
 // conv_split_pre, further down, is a COPY of conv_split (loader, mma, epilogue) that reads and / or writes the split activation form;
 // conv_split's code object is kept as it is, so the two are kept in step by hand: a change to the arithmetic, the K order or the
 // epilogue expressions of one belongs in the other, and tests/test_conv_presplit.py compares them bit for bit.
-#include "common.h"
+#include "conv_rows_core.h"      // the split-fp16 vocabulary (vector types, kKT, kThreads, the activation scale), split4, overlap
 
 namespace rmnet {
 namespace {
-
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef _Float16 half4 __attribute__((ext_vector_type(4)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));   // 16 bytes of packed weights (native vector: see conv3x3.hip)
-
-constexpr int kKT = 32;          // K per step (one tap x 32 input channels)
-constexpr int kThreads = 512;
-constexpr float kActScale = 64.0f;                 // 2^6
-constexpr float kActUnscale = 1.0f / 64.0f;
-constexpr float kF16Max = 65504.0f;
 
 // [row][32 halves] images (64-B rows), 16-byte chunk index XOR-swizzled with row bits 1..2 (conv3x3.hip's layout)
 __device__ inline int swz(int row, int chunk) { return row * kKT + ((chunk ^ ((row >> 1) & 3)) << 3); }
@@ -308,19 +297,8 @@ void launch(const SplitArgs& a, hipStream_t st) {
 // ------------------------------------------------------------------------------------------------ pre-split activations
 // The split ACTIVATION form (include/rmnet_hip.h): [M][C / 32][2][32] fp16 -- per pixel and block of 32 channels the 32 hi halves,
 // then the 32 lo halves, of c = clamp(64 * pre(v)).  A pixel has the byte stride it has in fp32, and every 16-byte chunk is 8 halves of
-// one plane: exactly a chunk of the LDS image.  split4 is store_x's per-element arithmetic, expression for expression.
-__device__ inline void split4(const f32x4 v, half4& hi, half4& lo, int& bad) {
-#pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    const float y = v[e] * kActScale;
-    bad += !(fabsf(y) <= kF16Max) ? 1 : 0;
-    const float c = fminf(fmaxf(y, -kF16Max), kF16Max);
-    const _Float16 h = (_Float16)c;
-    hi[e] = h;
-    lo[e] = (_Float16)(c - (float)h);
-  }
-}
-
+// one plane: exactly a chunk of the LDS image.  split4 (csrc/conv_rows_core.h) is store_x's per-element arithmetic, expression for
+// expression.
 struct PreArgs {
   const float* x;          // XS 0: [N][H][W][Cin] fp32
   const _Float16* xs;      // XS 1: [N][H][W][Cin / 32][2][32] fp16
@@ -639,12 +617,6 @@ __global__ __launch_bounds__(kSplitActThreads) void split_act(const float* __res
     *reinterpret_cast<half8*>(o + kKT) = lo;
   }
   if (range && bad) atomicAdd(range, bad);
-}
-
-inline bool overlap(const void* p, long long pn, const void* q, long long qn) {
-  const char* a = reinterpret_cast<const char*>(p);
-  const char* b = reinterpret_cast<const char*>(q);
-  return a < b + qn && b < a + pn;
 }
 
 }  // namespace

@@ -361,6 +361,26 @@ def test_launch_plan_invariants_on_the_host(tmp_path):
     assert run.returncode == 0 and 'plan_check ok' in run.stdout, run.stdout[-3000:]
 
 
+def test_library_rebuilds_after_an_edit_to_any_header_of_csrc(monkeypatch):
+    """build.needs_build(): the dependency list holds every header present in csrc/ (and every one a source includes by name, and the
+    C ABI's header), and a header newer than the library -- each in turn -- asks for a build."""
+    from rmnet_amd import build
+    deps = build.dependencies()
+    headers = sorted(f for f in os.listdir(build.CSRC) if f.endswith('.h'))
+    assert 'common.h' in headers and 'conv_rows_core.h' in headers
+    for s in build.SOURCES + headers:
+        headers += [h for h in re.findall(r'#include "([^"/]+\.h)"', open(os.path.join(build.CSRC, s)).read()) if h not in headers]
+    for h in headers:
+        assert os.path.join(build.CSRC, h) in deps, h
+    assert os.path.join(ROOT, 'include', 'rmnet_hip.h') in deps
+    assert all(os.path.join(build.CSRC, s) in deps for s in build.SOURCES)
+    real_exists = os.path.exists
+    monkeypatch.setattr(os.path, 'exists', lambda p: p == build.LIB or real_exists(p))
+    for newer in [None] + [os.path.join(build.CSRC, h) for h in headers]:
+        monkeypatch.setattr(os.path, 'getmtime', lambda p: 2.0 if p == newer else 1.0)
+        assert build.needs_build() is (newer is not None), newer
+
+
 def test_bench_becomes_its_own_launcher_for_several_gpus(monkeypatch):
     """`python bench.py --gpus N` from a plain shell (WORLD_SIZE unset): bench.py re-executes its own command line as N ranks under
     torch.distributed.run on 127.0.0.1 at a free port, with dmabuf IPC for RCCL, and hands the exit code back.  (The GPU suite runs
