@@ -399,6 +399,31 @@ int rmnet_conv_rows_pre_f32(const void *x, const void *wpack, const float *w_uns
 int rmnet_stem_split_f32(const float *frame, const float *mask, const float *other, const void *wpack, const float *w_unscale,
                          const float *shift, int N, int H, int W, float *out, int32_t *range_word, void *stream);
 
+/* C2 TinyFlowNet's front end (additive export, same ABI version): zero-padding of the two frames, the bilinear halving, the 6-channel
+ * concatenation, conv1 (7x7 / stride 2 / pad 3, 6 -> 64), its bias and LeakyReLU(0.1) in ONE launch (csrc/flow_stem.hip), on the
+ * split-fp16 arithmetic of rmnet_stem_split_f32; neither the padded frames nor the half-resolution pair is written.  Replaces
+ * pad_divide_by / F.interpolate / torch.cat / conv1 of TinyFlowNet._forward (models/tiny_flownet.py).
+ *   img0, img1 [N, 3, H, W] fp32, read in place, 4-byte aligned: frame n is a dense [3, H, W] block at img + n * batch_stride
+ *         floats (batch_stride0 / batch_stride1 >= 3*H*W, RMNET_E_INVALID_ARG otherwise), so frame t of a [N, T, 3, H, W] clip is
+ *         read without a copy;
+ *   Hpad, Wpad, lh, lw: the padded frame is [Hpad, Wpad] with the frame at rows lh .. lh+H-1 and columns lw .. lw+W-1 and zeros
+ *         elsewhere (lh, lw >= 0, lh + H <= Hpad, lw + W <= Wpad; RMNET_E_INVALID_ARG otherwise).  Hh = Hpad / 2, Wh = Wpad / 2;
+ *   pair  [N, 6, Hh, Wh] (never materialised): channel c < 3 from img0, 3 <= c < 6 from img1; element (Y, X) = 0.25 * ((p[2Y][2X] +
+ *         p[2Y][2X+1]) + (p[2Y+1][2X] + p[2Y+1][2X+1])) of the padded frame p -- F.interpolate(scale_factor=0.5, 'bilinear');
+ *   out   [N, Hc, Wc, 64] fp32 (channels-last) = leaky_0.1(conv7x7_s2_p3(pair) + bias[co]), Hc = (Hh - 1) / 2 + 1 (Wc alike);
+ *         must not overlap img0 or img1 (RMNET_E_INVALID_ARG);
+ *   bias  [64] may be NULL;
+ *   range_word: as above; every element of PAIR with |x| >= 1023.5, NaN or Inf is saturated and counted once.
+ * wpack, w_unscale, bias and out 16-byte aligned.  RMNET_E_UNSUPPORTED for an odd Hpad or Wpad and for N*3*H*W or N*Hc*Wc*64 >= 2^31;
+ * nothing is written on any refusal.  The kernel asks for 115296 B of dynamic LDS, which needs a function attribute: it is set at the
+ * first call on a device, and that first call must not come from a stream that is capturing (RMNET_E_UNSUPPORTED): call once eagerly
+ * before capturing.
+ *
+ * Weight pack (rmnet_amd.ops.flow_stem_pack) for w [64][6][7][7] fp32: rmnet_stem_split_f32's layout with Cin = 6:
+ *   k = (7 * ky + kx) * 6 + ci, 0 <= k < 294, zero-padded to Kp = 320;  wpack fp16 [10][2][64][32]  (81920 bytes). */
+int rmnet_flow_stem_f32(const float *img0, const float *img1, long long batch_stride0, long long batch_stride1, const void *wpack,
+                        const float *w_unscale, const float *bias, int N, int H, int W, int Hpad, int Wpad, int lh, int lw, float *out, int32_t *range_word, void *stream);
+
 /* C1 decoder prediction head (additive export, same ABI version): out = conv3x3_p1(relu(x), w) + bias with two output channels in
  * plain fp32 FMA (csrc/pred_head.hip).  Replaces F.relu(m2), Decoder.pred2 (models/rmnet.py:138-139) and the layout copy behind it.
  *   x    [n, Hq, Wq, C] fp32 (channels-last), C % 32 == 0, 16-byte aligned;  w [2][C][3][3], bias [2] fp32 (no pack);

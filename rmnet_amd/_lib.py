@@ -103,6 +103,9 @@ SIGNATURES = {
     'rmnet_stem_split_f32': (ctypes.c_int, [
         c_f32p, c_f32p, c_f32p, ctypes.c_void_p, c_f32p, c_f32p, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_f32p, c_i32p,
         ctypes.c_void_p]),
+    'rmnet_flow_stem_f32': (ctypes.c_int, [
+        c_f32p, c_f32p, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_void_p, c_f32p, c_f32p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+        ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_f32p, c_i32p, ctypes.c_void_p]),
     'rmnet_pred_head_f32': (ctypes.c_int, [
         c_f32p, c_f32p, c_f32p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_f32p, ctypes.c_void_p]),
     'rmnet_flow_conv_f32': (ctypes.c_int, [

@@ -279,10 +279,12 @@ class Decoder(nn.Module):
 
 
 # The stem and prediction-head kernels become part of the default path ('split') only on a measured win: per-step time in a kernel
-# trace below the dispatches they replace, and the bench line not below RMNET_CONV=trunk (profiles/r09_a_stem_head.md).  No such
-# measurement exists yet, so both are off by default and RMNET_CONV=full selects them.
-STEM_DEFAULT = False
-HEAD_DEFAULT = False
+# trace below the dispatches they replace, and the bench line not below RMNET_CONV=trunk (profiles/r09_a_stem_head.md).  Measured
+# in profiles/r23_a_front_ends.md, per frame step of the bench: the two stem launches 0.61 ms against 1.31 ms for the cat, the two
+# library convolutions and the two pool passes; the head 0.15 ms against 0.70 ms for the ReLU, pred2 and the layout copy; every
+# bench run with both above every run without.  RMNET_CONV=trunk switches both off.
+STEM_DEFAULT = True
+HEAD_DEFAULT = True
 
 
 def _stem_backends():

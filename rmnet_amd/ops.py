@@ -1137,6 +1137,83 @@ def stem_split(frame, mask=None, other=None, wpack=None, w_unscale=None, shift=N
     return out
 
 
+FLOW_STEM_CIN = 6                 # csrc/flow_stem.hip: the frame pair's channels
+FLOW_STEM_KP = 320                # 49 * 6 = 294 rounded up to a multiple of 32
+
+
+@torch.no_grad()
+def flow_stem_pack(weight):
+    """[64, 6, 7, 7] fp32 weight of TinyFlowNet's conv1 -> (wpack [320 * 64 * 2] fp16 bits as int16, w_unscale fp32 [64]) in
+    ``stem_pack``'s layout with Cin 6 (include/rmnet_hip.h, rmnet_flow_stem_f32): per-channel power-of-two scale, hi / lo split,
+    K index k = (7 * ky + kx) * 6 + ci zero-padded from 294 to 320, laid out as [k / 32][hi, lo][co][k % 32]."""
+    if tuple(weight.shape) != (STEM_COUT, FLOW_STEM_CIN, 7, 7):
+        raise RuntimeError('flow_stem_pack needs a [64, 6, 7, 7] weight, got %s' % (tuple(weight.shape),))
+    if weight.dtype != torch.float32:
+        raise RuntimeError('flow_stem_pack needs fp32 weights, got %s' % weight.dtype)
+    w = weight.detach().double()
+    amax = w.abs().amax(dim=(1, 2, 3))
+    _, ex = torch.frexp(amax)                              # amax in [2^(ex-1), 2^ex)
+    e = torch.where(amax > 0, 15 - ex, torch.zeros_like(ex))
+    ws = torch.ldexp(w, e.view(-1, 1, 1, 1).to(w.dtype))   # exact: power-of-two scaling
+    wk = torch.zeros(STEM_COUT, FLOW_STEM_KP, dtype=torch.float64, device=w.device)
+    wk[:, :49 * FLOW_STEM_CIN] = ws.permute(0, 2, 3, 1).reshape(STEM_COUT, 49 * FLOW_STEM_CIN)
+    hi = wk.half()
+    lo = (wk - hi.double()).half()
+    planes = torch.stack([p.reshape(STEM_COUT, FLOW_STEM_KP // 32, 32).permute(1, 0, 2) for p in (hi, lo)], dim=1)
+    unscale = torch.ldexp(torch.ones_like(amax), (-e).to(amax.dtype)).float()
+    return planes.contiguous().view(-1).view(torch.int16), unscale.contiguous()
+
+
+def flow_stem(img0, img1, wpack, w_unscale, bias=None, pad=(0, 0, 0, 0), range_word=None):
+    """leaky_relu(conv7x7_s2_p3(pair) + bias, 0.1) in one launch of csrc/flow_stem.hip -> channels-last fp32 [N, 64, Hc, Wc], where
+    ``pair`` = cat(halve(zero_pad(img0)), halve(zero_pad(img1))) is never built: ``img0, img1`` [N, 3, H, W] are read in place (every
+    frame a dense [3, H, W] block at any batch stride, e.g. ``clip[:, t]`` of a [N, T, 3, H, W] clip; other layouts are copied),
+    ``pad`` = (lw, uw, lh, uh) as ``helpers.pad_amounts`` returns it (the padded size must be even), the halving is
+    F.interpolate(scale_factor=0.5, 'bilinear') = a 2x2 mean.  ``wpack, w_unscale`` come from ``flow_stem_pack``; ``range_word``: as
+    for ``stem_split``, counted per element of the pair.  The first call on a device must not come from a capturing stream.  No
+    fall-back: anything else is a RuntimeError."""
+    for t, n in ((img0, 'img0'), (img1, 'img1')):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float32:
+            raise RuntimeError('%s must be a CUDA float32 tensor' % n)
+    if img0.dim() != 4 or img0.shape[1] != 3 or img1.shape != img0.shape:
+        raise RuntimeError('img0 and img1 must be [N, 3, H, W] of one shape')
+    N, _, H, W = img0.shape
+
+    def frames(t):       # dense [3, H, W] frames at a batch stride the kernel can step over, else a contiguous copy
+        ok = tuple(t.stride()[1:]) == (H * W, W, 1) and (N == 1 or t.stride(0) >= 3 * H * W)
+        return t if ok else t.contiguous()
+    img0, img1 = frames(img0), frames(img1)
+    bs0, bs1 = (max(int(t.stride(0)), 3 * H * W) if N > 1 else 3 * H * W for t in (img0, img1))
+    lw, uw, lh, uh = (int(p) for p in pad)
+    if min(lw, uw, lh, uh) < 0:
+        raise RuntimeError('flow_stem: negative pad %s' % (pad,))
+    hpad, wpad = H + lh + uh, W + lw + uw
+    _check(wpack, 'wpack', torch.int16)
+    if wpack.numel() != FLOW_STEM_KP * STEM_COUT * 2:
+        raise RuntimeError('wpack has %d elements, a flow stem pack has %d' % (wpack.numel(), FLOW_STEM_KP * STEM_COUT * 2))
+    _check(w_unscale, 'w_unscale')
+    if w_unscale.numel() != STEM_COUT:
+        raise RuntimeError('w_unscale must have 64 elements')
+    if bias is not None:
+        _check(bias, 'bias')
+        if bias.numel() != STEM_COUT:
+            raise RuntimeError('bias must have 64 elements')
+    if range_word is not None:
+        _check(range_word, 'range_word', torch.int32)
+    for t in (img1, wpack, w_unscale, bias, range_word):
+        if t is not None and t.device != img0.device:
+            raise RuntimeError('flow_stem: every tensor must be on %s' % img0.device)
+    hh, wh = hpad // 2, wpad // 2
+    out = torch.empty((N, STEM_COUT, (hh - 1) // 2 + 1, (wh - 1) // 2 + 1), dtype=img0.dtype, device=img0.device,
+                      memory_format=torch.channels_last)
+    lib = _lib.load()
+    with torch.cuda.device(img0.device):
+        rc = lib.rmnet_flow_stem_f32(_ptr(img0), _ptr(img1), bs0, bs1, _ptr(wpack), _ptr(w_unscale), _ptr(bias), N, H, W, hpad, wpad, lh, lw,
+                                     _ptr(out), _ptr(range_word), _stream(img0.device))
+    _lib.check(rc, 'rmnet_flow_stem_f32')
+    return out
+
+
 def pred_head(x, weight, bias):
     """conv3x3_p1(relu(x), weight) + bias for a channels-last fp32 ``x`` [n, C, Hq, Wq] (C % 32 == 0) and ``weight`` [2, C, 3, 3],
     ``bias`` [2] -> NCHW-contiguous [n, 2, Hq, Wq], plain fp32 FMA (csrc/pred_head.hip): the decoder's prediction head with its

@@ -364,9 +364,9 @@ class RMNet(nn.Module):
         into a HIP graph once and replayed for every frame (``forward`` does).
 
         After ``fuse_epilogues()`` on a channels-last network the ResNet-50 trunks' bottleneck convolutions, the key / value heads and
-        the decoder's 256-channel convolutions run on the split-fp16 kernels (``RMNET_CONV=decoder``: the decoder's only); with
-        ``RMNET_CONV=full`` so do the two encoder stems (7x7 convolution, BatchNorm, ReLU and max-pool in one launch), and the
-        prediction head runs on its fp32 kernel (both off by default until measured: ``networks.STEM_DEFAULT / HEAD_DEFAULT``).
+        the decoder's 256-channel convolutions run on the split-fp16 kernels (``RMNET_CONV=decoder``: the decoder's only); so do
+        the two encoder stems (7x7 convolution, BatchNorm, ReLU and max-pool in one launch), and the prediction head runs on its
+        fp32 kernel (``networks.STEM_DEFAULT / HEAD_DEFAULT``; ``RMNET_CONV=trunk`` leaves these two on the library).
         The split-fp16 kernels
         saturate activations outside |x| < 1023.5 and count them in ``ops.conv_range_word(device)``.  ``forward``
         zeroes and checks that word once per clip and redoes the clip on MIOpen when it is non-zero; a streaming caller of

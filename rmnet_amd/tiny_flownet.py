@@ -1,7 +1,8 @@
 # -*- coding: utf-8 -*-
 """TinyFlowNet on stock PyTorch-ROCm; on a fused channels-last network its ten wide convolutions run
 on a HIP kernel (csrc/flow_conv.hip, ``RMNET_FLOW_CONV``: see ``TinyFlowNet._forward``), and with ``RMNET_FLOW_CONV=full`` its four
-flow heads and three flow upsamplers as well (csrc/flow_head.hip).
+flow heads and three flow upsamplers as well (csrc/flow_head.hip); with ``RMNET_FLOW_STEM=1`` conv1 and the passes that build its
+input run as one launch of csrc/flow_stem.hip.
 
 Mirrors ``models/tiny_flownet.py`` of the reference: same constructor signature, same
 ``forward(frames) -> [B, N, 2, H, W]`` contract and the same state-dict keys
@@ -17,7 +18,7 @@ import torch
 import torch.nn.functional as F
 from torch import nn
 
-from .helpers import pad_divide_by
+from .helpers import pad_amounts, pad_divide_by
 
 
 def _conv(c_in, c_out, k, stride=1):
@@ -58,6 +59,25 @@ def flow_conv_backend():
     return v
 
 
+# conv1 with everything in front of it (two pads, two halvings, the 6-channel cat) and its bias + LeakyReLU in one launch of
+# csrc/flow_stem.hip with RMNET_FLOW_STEM=1.  The rule for the default is networks.STEM_DEFAULT's: per-step time in a kernel trace
+# below the dispatches it replaces, and every bench run above every run of the parent.  profiles/r23_a_front_ends.md has both
+# measurements; the default is still off because tests/test_flow_conv.py::test_the_switch_selects_the_path and
+# tests/test_flow_head.py::test_full_leaves_conv1_as_the_only_library_convolution pin conv1 as a library call on the default path
+# (as they pin FLOW_CONV_DEFAULT): switching it on goes together with a change of those two tests.
+FLOW_STEM_DEFAULT = False
+
+
+def flow_stem_enabled():
+    """RMNET_FLOW_STEM ('0' or '1', read at every call; unset: FLOW_STEM_DEFAULT).  Any other value is a RuntimeError."""
+    v = os.environ.get('RMNET_FLOW_STEM')
+    if v is None:
+        return FLOW_STEM_DEFAULT
+    if v.strip() not in ('0', '1'):
+        raise RuntimeError("RMNET_FLOW_STEM must be '0' or '1', got %r" % v)
+    return v.strip() == '1'
+
+
 class TinyFlowNet(nn.Module):
     def __init__(self, cfg=None):
         super().__init__()
@@ -92,7 +112,17 @@ class TinyFlowNet(nn.Module):
         synchronisation here (the call can be captured into a HIP graph): ``forward`` zeroes and checks the word once per clip, a
         streaming caller of ``_forward`` checks ``flow_range_count()`` itself and, when it is non-zero, zeroes the word and redoes
         the frames since its last check with ``RMNET_FLOW_CONV=miopen``.  ``RMNET_FLOW_CONV=full`` runs the flow heads and the flow
-        upsamplers on csrc/flow_head.hip as well (plain fp32, no window): conv1 is then the only library convolution."""
+        upsamplers on csrc/flow_head.hip as well (plain fp32, no window): conv1 is then the only library convolution.
+        Under the same conditions ``RMNET_FLOW_STEM=1`` runs conv1 on csrc/flow_stem.hip, which reads the two frames in place: the
+        pads, the halvings, the cat and the bias + LeakyReLU pass are not issued, and the elements of the frame pair outside the
+        window are counted in the same word.  Its first call on a device must not come from a capturing stream."""
+        if self._flow_stem_ok(img0, img1):
+            from . import ops
+            pad = pad_amounts(int(img0.shape[2]), int(img0.shape[3]), 64)
+            wp, wu = self._flow_stem_pack
+            c1 = ops.flow_stem(img0, img1, wp, wu, self.conv1[0].bias, pad=pad,
+                               range_word=self.flow_range_word(img0.device))
+            return self._unpad(self._refine_split(c1, full=flow_conv_backend() == 'full'), pad)
         (img0, img1), pad = pad_divide_by([img0, img1], 64, img0.shape[2:])
         pair = torch.cat((F.interpolate(img0, scale_factor=0.5, mode='bilinear'),
                           F.interpolate(img1, scale_factor=0.5, mode='bilinear')), dim=1)
@@ -110,8 +140,12 @@ class TinyFlowNet(nn.Module):
             cat3 = torch.cat((c3, run(self.deconv3, cat4), self.upsampled_flow4_to_3(self.predict_flow4(cat4))), 1)
             cat2 = torch.cat((c2, run(self.deconv2, cat3), self.upsampled_flow3_to_2(self.predict_flow3(cat3))), 1)
             flow2 = self.predict_flow2(cat2)
-        flow = F.interpolate(flow2, scale_factor=8, mode='bilinear')
+        return self._unpad(flow2, pad)
 
+    @staticmethod
+    def _unpad(flow2, pad):
+        """The x8 bilinear upsample of the 1/8-resolution flow and the crop back to the frame."""
+        flow = F.interpolate(flow2, scale_factor=8, mode='bilinear')
         lw, uw, lh, uh = pad
         if lh + uh > 0:
             flow = flow[:, :, lh:flow.shape[2] - uh, :]
@@ -134,6 +168,17 @@ class TinyFlowNet(nn.Module):
             return False
         backend = flow_conv_backend()
         return backend if backend in ('split', 'full') else False
+
+    def _flow_stem_ok(self, img0, img1):
+        """True when conv1 and the passes in front of it run on csrc/flow_stem.hip for this frame pair: RMNET_FLOW_STEM on, the
+        conditions of ``_flow_split_ok`` (the ten wide convolutions take the kernel's output), two frames of one shape and a
+        biased conv1 with its pack on the frames' device."""
+        if not flow_stem_enabled() or img0.dim() != 4 or img0.shape[1] != 3 or img1.shape != img0.shape or img1.dtype != img0.dtype:
+            return False
+        pack = getattr(self, '_flow_stem_pack', None)
+        if pack is None or pack[0].device != img0.device or img1.device != img0.device or self.conv1[0].bias is None:
+            return False
+        return bool(self._flow_split_ok(img0))
 
     def _refine_split(self, c1, full=False):
         """conv2 .. predict_flow2 on ``c1`` = conv1's output, the ten wide layers on the HIP kernel.  cat4 / cat3 / cat2 are ONE
@@ -219,7 +264,7 @@ class TinyFlowNet(nn.Module):
 
     @torch.no_grad()
     def _build_flow_packs(self):
-        """The ten weight packs, the zero-padded flow-head weights, the four flow-head packs and NCHW-contiguous upsampler weights
+        """The ten weight packs, conv1's pack for csrc/flow_stem.hip, the zero-padded flow-head weights, the four flow-head packs and NCHW-contiguous upsampler weights
         of csrc/flow_head.hip, and the range word: plain attributes (not parameters or buffers, so ``state_dict()`` is untouched),
         rebuilt whenever the parameters move (``_apply``) or are loaded."""
         from . import ops
@@ -232,6 +277,7 @@ class TinyFlowNet(nn.Module):
             w = getattr(self, 'predict_flow%d' % level).weight.detach()
             heads[level] = F.pad(w, (0, 0, 0, 0, 0, ld - w.shape[1])).contiguous(memory_format=torch.channels_last)
         self.__dict__['_flow_packs'] = packs
+        self.__dict__['_flow_stem_pack'] = ops.flow_stem_pack(self.conv1[0].weight.detach().float())
         self.__dict__['_flow_head_w'] = heads
         self.__dict__['_flow_head_packs'] = {level: ops.flow_head_pack(getattr(self, 'predict_flow%d' % level).weight.detach().float())
                                              for level in (5, 4, 3, 2)}
@@ -280,6 +326,7 @@ class TinyFlowNet(nn.Module):
             self._build_flow_packs()
         else:
             self.__dict__.pop('_flow_packs', None)
+            self.__dict__.pop('_flow_stem_pack', None)
             self.__dict__.pop('_flow_head_w', None)
             self.__dict__.pop('_flow_head_packs', None)
             self.__dict__.pop('_flow_up_w', None)
