@@ -518,6 +518,31 @@ int rmnet_flow_affine_f32_host(const float *flow_host, const float *m1_host, con
                                int H, int W, float *out_host, void *workspace,
                                size_t workspace_bytes, void *stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * E1  Boundary measure F: the four integer counts per (frame, object) (additive exports, same ABI version).
+ * Replaces: Metrics._get_f_score and Metrics.seg2bmap, utils/metrics.py:119-226, up to the counts -- the boundary maps of
+ *           both masks, their dilation by skimage.morphology.disk(radius) and the sums of utils/metrics.py:147-152 -- for
+ *           every object of every frame at once and without taking a label map off the device (csrc/boundary_f.hip).
+ *           Precision, recall and F follow from the counts (utils/metrics.py:155-169: rmnet_amd.metrics.f_from_counts).
+ *   pred, gt  [N,H,W] uint8 label maps, 0 = background; object k = (label == k) for k = 1 .. K, a label above K belongs
+ *             to no object.
+ *   radius    the disk's radius in pixels, ceil(0.008 * |(H, W)|) by the reference's rule (utils/metrics.py:134-135):
+ *             8 at 480x854, 18 at 1080x1920, 36 at 2160x3840.  Offsets (dy, dx) with dx^2 + dy^2 <= radius^2; 0 = the
+ *             centre tap alone.  The dilation reads 0 outside the image.
+ *   counts    [N,K,4] int32 out: (n_fg, n_gt, fg_match, gt_match) = |bmap(pred_k)|, |bmap(gt_k)|,
+ *             |bmap(pred_k) & dilate(bmap(gt_k))|, |bmap(gt_k) & dilate(bmap(pred_k))| with bmap = seg2bmap at the map's
+ *             own size (utils/metrics.py:202-213).  Fully written (no pre-zeroing needed); exact integers, the same bits
+ *             from call to call.
+ *   workspace 8-byte aligned, at least rmnet_boundary_match_workspace_bytes(N, K, H, W) bytes (0 when any size is <= 0):
+ *             the boundary maps as bit rows, [N][K][2][H][ceil(W/64)] 64-bit words.
+ * RMNET_E_INVALID_ARG for a NULL pred / gt / counts, a non-positive size or a misaligned workspace; RMNET_E_UNSUPPORTED
+ * for K > 64, radius < 0, radius > 40 or a launch of more than 2^31 - 1 workgroups (N*ceil(H/8)*ceil(W/64) / 4 or N*K*ceil(H*ceil(W/64) / 256));
+ * RMNET_E_WORKSPACE for a NULL or short workspace.
+ * ------------------------------------------------------------------------------------------- */
+size_t rmnet_boundary_match_workspace_bytes(int N, int K, int H, int W);
+int rmnet_boundary_match_u8(const uint8_t *pred, const uint8_t *gt, int N, int K, int H, int W, int radius, int32_t *counts,
+                            void *workspace, size_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -123,6 +123,10 @@ SIGNATURES = {
     'rmnet_flow_affine_f32_host': (ctypes.c_int, [
         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
+    'rmnet_boundary_match_workspace_bytes': (ctypes.c_size_t, [ctypes.c_int] * 4),
+    'rmnet_boundary_match_u8': (ctypes.c_int, [
+        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_i32p,
+        ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
 }
 
 ABI_VERSION = 6

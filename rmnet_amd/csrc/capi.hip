@@ -233,4 +233,14 @@ int rmnet_flow_affine_f32_host(const float* flow_host, const float* m1_host, con
   return RMNET_OK;
 }
 
+size_t rmnet_boundary_match_workspace_bytes(int N, int K, int H, int W) {
+  if (N <= 0 || K <= 0 || H <= 0 || W <= 0) return 0;
+  return boundary_match_ws_bytes(N, K, H, W);
+}
+
+int rmnet_boundary_match_u8(const uint8_t* pred, const uint8_t* gt, int N, int K, int H, int W, int radius, int32_t* counts,
+                            void* workspace, size_t workspace_bytes, void* stream) {
+  return launch_boundary_match(pred, gt, N, K, H, W, radius, counts, workspace, workspace_bytes, static_cast<hipStream_t>(stream));
+}
+
 }  // extern "C"

@@ -404,6 +404,11 @@ int launch_bank_main(const BankReadArgs& a, hipStream_t st);   // bank.hip: the 
 size_t bank_read_ws_bytes(int no, int h, int w);
 int launch_bank_read(BankReadArgs& a, hipStream_t st);         // memory_read.hip: workspace carving + launch_bank_main
 
+// boundary_f.hip: the counts behind the boundary measure F, [N][K][4] = (n_fg, n_gt, fg_match, gt_match)
+size_t boundary_match_ws_bytes(int N, int K, int H, int W);
+int launch_boundary_match(const uint8_t* pred, const uint8_t* gt, int N, int K, int H, int W, int radius, int32_t* counts, void* ws,
+                          size_t ws_bytes, hipStream_t st);
+
 inline int check_launch() { return hipGetLastError() == hipSuccess ? RMNET_OK : RMNET_E_LAUNCH; }
 
 }  // namespace rmnet

@@ -1302,3 +1302,26 @@ def update_optical_flow(optical_flow, tr_matrix1, tr_matrix2, device=None):
                                             out.ctypes.data, _ptr(ws), ws.numel(), _stream(dev))
     _lib.check(rc, 'rmnet_flow_affine_f32_host')
     return out
+
+
+def boundary_match(pred, gt, n_objects, radius):
+    """pred, gt: uint8 [N,H,W] label maps on the GPU (0 = background) -> int32 [N, n_objects, 4], per frame and object
+    k = 1 .. n_objects the counts (n_fg, n_gt, fg_match, gt_match) behind the boundary measure F of utils/metrics.py:119-169:
+    the sizes of the two boundary maps and of each one's part inside the other's dilation by disk(radius) (csrc/boundary_f.hip,
+    include/rmnet_hip.h E1).  Exact integers; 1 <= n_objects <= 64, 0 <= radius <= 40."""
+    _check(pred, 'pred', dtype=torch.uint8)
+    _check(gt, 'gt', dtype=torch.uint8)
+    if pred.shape != gt.shape or pred.dim() != 3:
+        raise RuntimeError('expected two [N, H, W] label maps of the same shape')
+    if gt.device != pred.device:
+        raise RuntimeError('pred and gt must be on the same device')
+    lib = _lib.load()
+    N, H, W = pred.shape
+    K, dev = int(n_objects), pred.device
+    with torch.cuda.device(dev):
+        counts = torch.empty(N, max(K, 0), 4, dtype=torch.int32, device=dev)
+        ws = _ws(lib.rmnet_boundary_match_workspace_bytes(N, K, H, W), dev)
+        rc = lib.rmnet_boundary_match_u8(_ptr(pred), _ptr(gt), N, K, H, W, int(radius), _ptr(counts), _ptr(ws), ws.numel(),
+                                         _stream(dev))
+    _lib.check(rc, 'rmnet_boundary_match_u8')
+    return counts
