@@ -543,6 +543,51 @@ size_t rmnet_boundary_match_workspace_bytes(int N, int K, int H, int W);
 int rmnet_boundary_match_u8(const uint8_t *pred, const uint8_t *gt, int N, int K, int H, int W, int radius, int32_t *counts,
                             void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * F1  Clip I/O: uint8 frames and label maps in, uint8 label maps and overlay frames out (additive exports, same ABI
+ *     version; csrc/clip_io.hip).  Every result equals the reference's host arithmetic bit for bit.
+ * Replaces: the loader's Normalize / ToOneHot after ReorganizeObjectID (utils/data_transforms.py:53-96 with
+ *           img_normalize and to_onehot, utils/helpers.py:81-90, 133-135), torch.argmax over the probabilities and
+ *           get_segmentation (core/inference.py:62-70, utils/helpers.py:138-178) up to the PNG encoder.
+ * mean, std are HOST pointers to three doubles (the configuration's DATASET_MEAN / DATASET_STD); every other pointer is a
+ * device pointer.  A lane owns 4 consecutive pixels (16 for the one-hot planes) when H*W and the pointers' alignment allow
+ * dword / 16-byte accesses, and one pixel otherwise: any contiguous tensor is accepted.
+ *
+ * rmnet_frames_normalize_u8: frames [N,H,W,3] uint8 -> out [N,3,H,W] f32 with
+ *     x = fl32(float(u) / 255.0f);  y = fl32((double(x) - mean[c]) / std[c])        (one rounding per operation)
+ * rmnet_labels_onehot_u8: labels [N,H,W] uint8 -> out [N,K,H,W] uint8, out[n,k,y,x] = (lut[label] == k); lut is a device
+ *     table of 256 uint8 or NULL for the identity.  A remapped label >= K sets no plane.  Fully written.
+ *     ReorganizeObjectID's table: the ids present in the clip without the ignore id, ascending, map to 0, 1, 2, ...;
+ *     every other id maps to 0 (rmnet_amd.clip_io.reorganize_lut builds it on the device).
+ * rmnet_argmax_labels_f32: prob [N,K,H,W] f32 -> labels [N,H,W] uint8, the FIRST index of the maximum over K
+ *     (torch.argmax's rule on ties).  1 <= K <= 255.  NaN inputs are out of scope: the inputs are soft-max outputs, and
+ *     a NaN never compares greater, so it is passed over.
+ * rmnet_overlay_u8: frames [N,3,H,W] f32 (the normalised frames the network consumed), labels [N,H,W] uint8
+ *     -> out [N,H,W,3] uint8, per frame get_segmentation(frame, mask, {mean, std}, ignore_idx, alpha):
+ *       denormalise   v_c = (uint8) trunc((double(x_c) * std[c] + mean[c]) * 255.0), three separately rounded operations
+ *                     (this is not the source byte: some forty values per channel come back one lower).  Defined for
+ *                     results in (-1, 256); saturates outside, NaN gives 0.
+ *       S             the labels present in the frame, minus the smallest one present (np.unique(mask)[1:]: background
+ *                     when there is any, otherwise the lowest object), minus ignore_idx.
+ *       events        the pixel's own label L and the labels of its 4-neighbours inside the image, those in S, ascending:
+ *                     o == L: v_c = (uint8) trunc(double(v_c) * alpha + (1.0 - alpha) * double(PALETTE[o][c]));
+ *                     o != L: v = 0 (the pixel is on o's contour, binary_dilation(mask == o) ^ (mask == o)).
+ *       PALETTE       the 16 DAVIS colours, then grey [i, i, i].  No product and sum is fused.
+ *     workspace: int32 [N], 4-byte aligned, at least N * 4 bytes; the entry writes every frame's smallest label into it in
+ *     two small launches ahead of the overlay launch (a fill with 255, then integer atomic minima).  It needs no
+ *     initialisation by the caller, holds the same bits after every call and the three launches can be captured in a graph.
+ *     An ignore_idx outside 0 .. 255 matches no label.
+ * RMNET_E_INVALID_ARG for a NULL pointer (lut excepted), a non-positive size, alpha outside [0, 1], std[c] == 0 or a
+ * pointer not aligned to its element type; RMNET_E_UNSUPPORTED for K > 255 or a launch of more than 2^31 - 1 workgroups
+ * (N * ceil(H*W / 256) for one-pixel lanes); RMNET_E_WORKSPACE for a NULL or short workspace.
+ * ------------------------------------------------------------------------------------------- */
+int rmnet_frames_normalize_u8(const uint8_t *frames, int N, int H, int W, const double *mean, const double *std, float *out,
+                              void *stream);
+int rmnet_labels_onehot_u8(const uint8_t *labels, const uint8_t *lut, int N, int K, int H, int W, uint8_t *out, void *stream);
+int rmnet_argmax_labels_f32(const float *prob, int N, int K, int H, int W, uint8_t *labels, void *stream);
+int rmnet_overlay_u8(const float *frames, const uint8_t *labels, int N, int H, int W, const double *mean, const double *std,
+                     double alpha, int ignore_idx, uint8_t *out, int32_t *workspace, size_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

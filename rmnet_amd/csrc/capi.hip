@@ -243,4 +243,23 @@ int rmnet_boundary_match_u8(const uint8_t* pred, const uint8_t* gt, int N, int K
   return launch_boundary_match(pred, gt, N, K, H, W, radius, counts, workspace, workspace_bytes, static_cast<hipStream_t>(stream));
 }
 
+int rmnet_frames_normalize_u8(const uint8_t* frames, int N, int H, int W, const double* mean, const double* std, float* out,
+                              void* stream) {
+  return launch_frames_normalize(frames, N, H, W, mean, std, out, static_cast<hipStream_t>(stream));
+}
+
+int rmnet_labels_onehot_u8(const uint8_t* labels, const uint8_t* lut, int N, int K, int H, int W, uint8_t* out, void* stream) {
+  return launch_labels_onehot(labels, lut, N, K, H, W, out, static_cast<hipStream_t>(stream));
+}
+
+int rmnet_argmax_labels_f32(const float* prob, int N, int K, int H, int W, uint8_t* labels, void* stream) {
+  return launch_argmax_labels(prob, N, K, H, W, labels, static_cast<hipStream_t>(stream));
+}
+
+int rmnet_overlay_u8(const float* frames, const uint8_t* labels, int N, int H, int W, const double* mean, const double* std,
+                     double alpha, int ignore_idx, uint8_t* out, int32_t* workspace, size_t workspace_bytes, void* stream) {
+  return launch_overlay(frames, labels, N, H, W, mean, std, alpha, ignore_idx, out, workspace, workspace_bytes,
+                        static_cast<hipStream_t>(stream));
+}
+
 }  // extern "C"

@@ -409,6 +409,13 @@ size_t boundary_match_ws_bytes(int N, int K, int H, int W);
 int launch_boundary_match(const uint8_t* pred, const uint8_t* gt, int N, int K, int H, int W, int radius, int32_t* counts, void* ws,
                           size_t ws_bytes, hipStream_t st);
 
+// clip_io.hip
+int launch_frames_normalize(const uint8_t* frames, int N, int H, int W, const double* mean, const double* std, float* out, hipStream_t st);
+int launch_labels_onehot(const uint8_t* labels, const uint8_t* lut, int N, int K, int H, int W, uint8_t* out, hipStream_t st);
+int launch_argmax_labels(const float* prob, int N, int K, int H, int W, uint8_t* labels, hipStream_t st);
+int launch_overlay(const float* frames, const uint8_t* labels, int N, int H, int W, const double* mean, const double* std, double alpha,
+                   int ignore_idx, uint8_t* out, int32_t* ws, size_t ws_bytes, hipStream_t st);
+
 inline int check_launch() { return hipGetLastError() == hipSuccess ? RMNET_OK : RMNET_E_LAUNCH; }
 
 }  // namespace rmnet

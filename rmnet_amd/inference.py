@@ -8,8 +8,11 @@ device-resident frame loop on them, and only the uint8 label maps -- or, with gr
 scalars -- cross RCCL at the end.  No communication while a clip runs.
 """
 
+import os
+
 import torch
 
+from . import clip_io
 from . import dist as rd
 from . import metrics
 
@@ -33,6 +36,55 @@ def segment_video(net, flownet, video, memorize_every=5):
     flows = flownet(frames)
     est = net(frames, masks, flows, n_objects, memorize_every, device=dev)
     return est[0].argmax(dim=1).to(torch.uint8)
+
+
+@torch.no_grad()
+def segment_video_u8(net, flownet, frames_u8, labels_u8, n_max_objects, mean, std, memorize_every=5, overlay=True):
+    """One clip from what a folder of images holds to what the reference's driver writes (core/inference.py:50-71 with the test
+    loader in front of it, utils/data_loaders.py:40-71), without leaving the device: ``frames_u8`` uint8 [N,H,W,3] RGB,
+    ``labels_u8`` uint8 palette label maps [N,H,W] or the first frame's [H,W] (only frame 0 is read by the network; the object ids
+    are reorganised over whatever is given, as ReorganizeObjectID does over the clip).  Returns {'labels': uint8 [N,H,W],
+    'overlay': uint8 [N,H,W,3] or None, 'n_objects': int} with the tensors on the model's device.  ``n_objects`` =
+    min(ids in the label maps - 1, n_max_objects) (utils/data_loaders.py:64) costs the one host synchronisation of the call."""
+    dev = next(net.parameters()).device
+    frames_u8 = frames_u8.to(dev, non_blocking=True).contiguous()
+    labels_u8 = labels_u8.to(dev, non_blocking=True)
+    if labels_u8.dim() == 2:
+        labels_u8 = labels_u8.unsqueeze(0)
+    labels_u8 = labels_u8.contiguous()
+    N = frames_u8.shape[0]
+    frames = clip_io.normalize_frames(frames_u8, mean, std)
+    lut, n_ids = clip_io.reorganize_lut(labels_u8)
+    masks = clip_io.onehot_labels(labels_u8, int(n_max_objects) + 1, lut)
+    if masks.shape[0] != N:
+        masks = masks[:1].expand(N, -1, -1, -1)                      # frame 0 is the only one the network reads
+    n_objects = min(int(n_ids) - 1, int(n_max_objects))
+    if n_objects < 0:
+        raise RuntimeError('the label maps hold no id but the ignored one: there is nothing to segment')
+    clip = frames.unsqueeze(0)
+    flows = flownet(clip)
+    est = net(clip, masks.unsqueeze(0), flows, torch.full((1, N), n_objects, dtype=torch.long), memorize_every, device=dev)
+    labels = clip_io.argmax_labels(est[0].contiguous())
+    return {'labels': labels, 'overlay': clip_io.overlay(frames, labels, mean, std) if overlay else None, 'n_objects': n_objects}
+
+
+def write_segmentations(folder, images):
+    """Write ``images`` as ``%05d.png`` into ``folder`` (created when missing), like core/inference.py:56-71: uint8 label maps
+    [N,H,W] as P-mode images with the DAVIS palette, uint8 overlays [N,H,W,3] as RGB.  Returns the paths."""
+    from PIL import Image
+    images = images.detach().to('cpu', torch.uint8).numpy()
+    if images.ndim not in (3, 4) or (images.ndim == 4 and images.shape[3] != 3):
+        raise RuntimeError('expected label maps [N, H, W] or overlays [N, H, W, 3]')
+    os.makedirs(folder, exist_ok=True)
+    palette = clip_io.PALETTE.reshape(-1).tolist()
+    paths = []
+    for i, array in enumerate(images):
+        image = Image.fromarray(array)
+        if array.ndim == 2:
+            image.putpalette(palette)
+        paths.append(os.path.join(folder, '%05d.png' % i))
+        image.save(paths[-1])
+    return paths
 
 
 def segment_videos(videos, segment_fn, rank=None, world_size=None, gather=True, dst=0):

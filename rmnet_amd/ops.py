@@ -1325,3 +1325,86 @@ def boundary_match(pred, gt, n_objects, radius):
                                          _stream(dev))
     _lib.check(rc, 'rmnet_boundary_match_u8')
     return counts
+
+
+# ------------------------------------------------------------------------------------------------ clip I/O (csrc/clip_io.hip)
+def _three_doubles(v, name):
+    v = [float(x) for x in v]
+    if len(v) != 3:
+        raise RuntimeError('%s must hold three numbers' % name)
+    return (ctypes.c_double * 3)(*v)
+
+
+def frames_normalize(frames, mean, std):
+    """frames uint8 [N,H,W,3] on the GPU -> float32 [N,3,H,W]: fl32(u / 255.f), then fl32((double(x) - mean[c]) / std[c]), the bits
+    of img_normalize + astype(float32) (utils/helpers.py:133-135, utils/data_transforms.py:93; include/rmnet_hip.h F1)."""
+    _check(frames, 'frames', dtype=torch.uint8)
+    if frames.dim() != 4 or frames.shape[3] != 3:
+        raise RuntimeError('frames must be [N, H, W, 3]')
+    lib = _lib.load()
+    N, H, W, _ = frames.shape
+    dev = frames.device
+    with torch.cuda.device(dev):
+        out = torch.empty(N, 3, H, W, dtype=torch.float32, device=dev)
+        rc = lib.rmnet_frames_normalize_u8(_ptr(frames), N, H, W, _three_doubles(mean, 'mean'), _three_doubles(std, 'std'), _ptr(out),
+                                           _stream(dev))
+    _lib.check(rc, 'rmnet_frames_normalize_u8')
+    return out
+
+
+def labels_onehot(labels, K, lut=None):
+    """labels uint8 [N,H,W] on the GPU -> uint8 [N,K,H,W], plane k = (lut[label] == k); ``lut`` is a uint8 [256] device table or None
+    for the identity.  A remapped label >= K sets no plane (utils/helpers.py:81-90).  1 <= K <= 255."""
+    _check(labels, 'labels', dtype=torch.uint8)
+    if labels.dim() != 3:
+        raise RuntimeError('labels must be [N, H, W]')
+    if lut is not None:
+        _check(lut, 'lut', dtype=torch.uint8)
+        if lut.numel() != 256 or lut.device != labels.device:
+            raise RuntimeError('lut must hold 256 entries on the device of labels')
+    lib = _lib.load()
+    N, H, W = labels.shape
+    K, dev = int(K), labels.device
+    with torch.cuda.device(dev):
+        out = torch.empty(N, max(K, 0), H, W, dtype=torch.uint8, device=dev)
+        rc = lib.rmnet_labels_onehot_u8(_ptr(labels), _ptr(lut), N, K, H, W, _ptr(out), _stream(dev))
+    _lib.check(rc, 'rmnet_labels_onehot_u8')
+    return out
+
+
+def argmax_labels(prob):
+    """prob float32 [N,K,H,W] on the GPU -> uint8 [N,H,W], the first index of the maximum over K (torch.argmax's rule on ties) in
+    one pass.  1 <= K <= 255; NaN inputs are out of scope."""
+    _check(prob, 'prob')
+    if prob.dim() != 4:
+        raise RuntimeError('prob must be [N, K, H, W]')
+    lib = _lib.load()
+    N, K, H, W = prob.shape
+    dev = prob.device
+    with torch.cuda.device(dev):
+        out = torch.empty(N, H, W, dtype=torch.uint8, device=dev)
+        rc = lib.rmnet_argmax_labels_f32(_ptr(prob), N, K, H, W, _ptr(out), _stream(dev))
+    _lib.check(rc, 'rmnet_argmax_labels_f32')
+    return out
+
+
+def overlay(frames, labels, mean, std, ignore_idx=255, alpha=0.4):
+    """frames float32 [N,3,H,W] (normalised), labels uint8 [N,H,W], both on the GPU -> uint8 [N,H,W,3]: get_segmentation of every
+    frame (utils/helpers.py:165-176) bit for bit -- denormalise, blend every object but the frame's lowest label with the palette,
+    blacken the 4-neighbour contours, in ascending object order (include/rmnet_hip.h F1)."""
+    _check(frames, 'frames')
+    _check(labels, 'labels', dtype=torch.uint8)
+    if frames.dim() != 4 or frames.shape[1] != 3 or labels.dim() != 3 or labels.shape != frames.shape[:1] + frames.shape[2:]:
+        raise RuntimeError('expected frames [N, 3, H, W] and labels [N, H, W]')
+    if labels.device != frames.device:
+        raise RuntimeError('frames and labels must be on the same device')
+    lib = _lib.load()
+    N, _, H, W = frames.shape
+    dev = frames.device
+    with torch.cuda.device(dev):
+        out = torch.empty(N, H, W, 3, dtype=torch.uint8, device=dev)
+        ws = torch.empty(max(N, 1), dtype=torch.int32, device=dev)
+        rc = lib.rmnet_overlay_u8(_ptr(frames), _ptr(labels), N, H, W, _three_doubles(mean, 'mean'), _three_doubles(std, 'std'),
+                                  float(alpha), int(ignore_idx), _ptr(out), _ptr(ws), ws.numel() * 4, _stream(dev))
+    _lib.check(rc, 'rmnet_overlay_u8')
+    return out
