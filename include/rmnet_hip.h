@@ -59,6 +59,10 @@ const char *rmnet_error_string(int code);
  *            (models/rmnet.py:245, 307, 356); empty boxes and channel 0 give (1,0,1,0).
  *            cells_h x cells_w is the feature-grid size.
  * Outputs are fully written (no pre-zeroing needed).  Integer outputs are bit-exact.
+ * RMNET_E_INVALID_ARG for a NULL mask / bboxes, a non-positive size, H or W > 32767 (the reference's box search starts
+ * from 32767) and cell_rects with a non-positive cell_stride / cells_h / cells_w; RMNET_E_UNSUPPORTED for B or K > 65535;
+ * RMNET_E_WORKSPACE for a NULL workspace or one shorter than rmnet_region_map_workspace_bytes(B, K, H, W), which needs
+ * no initialisation.  Nothing is written on any refusal.
  * ------------------------------------------------------------------------------------------- */
 size_t rmnet_region_map_workspace_bytes(int B, int K, int H, int W);
 int rmnet_region_map_f32(const float *mask, int B, int K, int H, int W, float prob_threshold,
@@ -73,7 +77,8 @@ int rmnet_region_map_f32(const float *mask, int B, int K, int H, int W, float pr
  * displacement in pixels), everything else as rmnet_region_map_f32.  The warp follows the arithmetic
  * PyTorch-ROCm executes for warp(): bilinear, align_corners=True, zero padding, validity of the
  * sampling footprint thresholded at 0.9999.  `warped` (optional, [B,K,H,W], channel 0 untouched)
- * receives the warped mask itself.  Same workspace size as rmnet_region_map_f32. */
+ * receives the warped mask itself.  Same workspace size and argument rules as rmnet_region_map_f32; a NULL flow is
+ * RMNET_E_INVALID_ARG, with or without `warped`. */
 int rmnet_region_map_warped_f32(const float *mask, const float *flow, int B, int K, int H, int W,
                                 float prob_threshold, int n_pts_threshold, int n_bbox_loose_pixels,
                                 float *att_map, int32_t *bboxes, int32_t *cell_rects, int pad_l,
@@ -507,9 +512,12 @@ int rmnet_soft_aggregate_f32(const float *dec, const int32_t *obj_begin, int B, 
  *   flow [H,W,2] f32, m1/m2 [2,3] f32 -> out [H,W,2] f32 (integer-valued).  Bit-exact with the
  *   reference's fp32 arithmetic (no FMA contraction, round-half-away-from-zero), including its
  *   quirk that y1 is computed from the already-updated x1 (.cpp:72-73).
- * _host variant: all four pointers are HOST pointers (the reference's NumPy calling convention);
- * it stages through `workspace` (device, >= rmnet_flow_affine_workspace_bytes) and synchronises
- * the stream before returning.
+ *   Alignment: flow and out 8-byte aligned (a pixel is read and written as one 8-byte access), m1 and m2 4-byte aligned;
+ *   RMNET_E_INVALID_ARG otherwise, before any launch.
+ * _host variant: all four pointers are HOST pointers (the reference's NumPy calling convention, any alignment a float
+ * array has); it stages through `workspace` (device, >= rmnet_flow_affine_workspace_bytes, 8-byte aligned:
+ * RMNET_E_INVALID_ARG otherwise, nothing copied) and synchronises the stream before returning.  Its staging pointers lie
+ * at workspace, workspace + 256 and workspace + 256 + 8*H*W, so an 8-byte aligned workspace meets the rule above.
  * ------------------------------------------------------------------------------------------- */
 int rmnet_flow_affine_f32(const float *flow, const float *m1, const float *m2, int H, int W,
                           float *out, void *stream);

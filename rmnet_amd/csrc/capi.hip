@@ -217,6 +217,9 @@ int rmnet_flow_affine_f32_host(const float* flow_host, const float* m1_host, con
     return RMNET_E_INVALID_ARG;
   if (!workspace || workspace_bytes < rmnet_flow_affine_workspace_bytes(H, W))
     return RMNET_E_WORKSPACE;
+  // d_m, d_in and d_out below lie at base, base + 256 and base + 256 + 8*H*W: an 8-byte aligned workspace gives
+  // launch_flow_affine the alignment it asks for, and it is checked here, ahead of the first copy
+  if ((reinterpret_cast<uintptr_t>(workspace) & 7) != 0) return RMNET_E_INVALID_ARG;
   hipStream_t st = static_cast<hipStream_t>(stream);
   const size_t nb = (size_t)H * W * 2 * sizeof(float);
   char* base = static_cast<char*>(workspace);

@@ -27,8 +27,9 @@ namespace {
 constexpr int kThreads = 256;
 
 // std::round (half away from zero), exactly.  The device library's roundf evaluates
-// trunc(x + copysign(0.5, x)), which rounds 3.4999998f up to 4 (the add is inexact); x - trunc(x)
-// is always exact, so this form has no such case.
+// trunc(x + copysign(0.5, x)), which rounds 0.49999997f (the fp32 number below 0.5) up to 1: the add is
+// inexact there, 1 - 2^-25 ties to 1.0.  (3.4999998f, named here before, is not such a case: 4 - 2^-22 is
+// representable; tests/test_region_edges.py carries both.)  x - trunc(x) is always exact, so this form has none.
 __device__ inline float round_half_away(float x) {
   float t = truncf(x);
   const float d = x - t;
@@ -71,6 +72,10 @@ __global__ __launch_bounds__(kThreads) void flow_affine_kernel(const float2* __r
 int launch_flow_affine(const float* flow, const float* m1, const float* m2, int H, int W,
                        float* out, hipStream_t st) {
   if (!flow || !m1 || !m2 || !out || H <= 0 || W <= 0) return RMNET_E_INVALID_ARG;
+  // the kernel reads and writes a pixel as one float2 (8 bytes) and the matrices as floats
+  if (((reinterpret_cast<uintptr_t>(flow) | reinterpret_cast<uintptr_t>(out)) & 7) != 0 ||
+      ((reinterpret_cast<uintptr_t>(m1) | reinterpret_cast<uintptr_t>(m2)) & 3) != 0)
+    return RMNET_E_INVALID_ARG;
   if (H >= (1 << 24) || W >= (1 << 24)) return RMNET_E_UNSUPPORTED;  // int -> float must be exact
   dim3 g((W + kThreads - 1) / kThreads, H < 4096 ? H : 4096);
   hipLaunchKernelGGL(flow_affine_kernel, g, dim3(kThreads), 0, st,
