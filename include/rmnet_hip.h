@@ -344,7 +344,7 @@ int rmnet_conv_split_f32(const float *x, const void *wpack, const float *w_unsca
 
 /* C1 pre-split activations (additive export, same ABI version).  rmnet_conv_split_f32 splits every activation it reads at every tap
  * and in every Cout tile; the split depends on the element alone, so a tensor that only such convolutions read can be kept in split
- * form and split once (csrc/conv_split.hip: conv_split_pre, split_act).
+ * form and split once (csrc/conv_split.hip: the XS / OS instances of the one kernel template conv_split, and split_act).
  *
  * The split ACTIVATION form of an NHWC activation v [M][C] fp32, C % 32 == 0, is [M][C / 32][2][32] fp16: per pixel and block of 32
  * channels the 32 hi halves, then the 32 lo halves, of
@@ -353,7 +353,8 @@ int rmnet_conv_split_f32(const float *x, const void *wpack, const float *w_unsca
  * per element like fp32, a pixel has the same byte stride, and every aligned 16-byte chunk holds 8 halves of one plane.  An element
  * with !(fabsf(y) <= 65504) adds one to the range word where the form is PRODUCED, once; a consumer counts nothing.
  *
- * rmnet_conv_split_pre_f32: rmnet_conv_split_f32 with two more flag bits -- the same tiles, arithmetic, K order, epilogue and results.
+ * rmnet_conv_split_pre_f32: rmnet_conv_split_f32 with two more flag bits -- the same kernel template, so the same tiles, arithmetic,
+ * K order, epilogue and results; both entries share one set of argument rules.
  *   RMNET_CONV_X_SPLIT    x is in split form.  RMNET_CONV_RELU_IN is then refused (the producer applied it), and the convolution
  *                         adds nothing to the range word for its input;
  *   RMNET_CONV_OUT_SPLIT  out receives act(conv + shift + res) in split form instead of fp32 and the elements of it outside the

@@ -56,32 +56,17 @@
 //   registers      weights 2 sets x 4 fragments x 4 VGPRs (this step's, the next step's), activations' prefetch 8, X fragments 16
 //   MFMA           per wave 8 x 2 tiles x 3 terms = 48, the same 1536 clk per step and SIMD; the ceiling above is unchanged.
 // Measured (profiles/r19_a_conv3x3_wreg.md): 4-7 % less time per call than conv3x3_split, the same bits.
-#include "common.h"
+#include "split_f16.h"      // the vector types, kKT, kThreads, the activation scale, swz
 
 namespace rmnet {
 namespace {
 
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef _Float16 half4 __attribute__((ext_vector_type(4)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));   // 16 bytes of packed weights.  A native vector: an array of HIP's
-                                                                    // uint4 (a struct) is not kept in registers but placed in LDS
-
 constexpr int kCout = 256;       // output channels (fixed)
 constexpr int kMT = 128;         // pixels per workgroup
-constexpr int kKT = 32;          // K per step (one tap x 32 input channels)
-constexpr int kThreads = 512;
-constexpr float kActScale = 64.0f;                 // 2^6
-constexpr float kActUnscale = 1.0f / 64.0f;
-constexpr float kF16Max = 65504.0f;
 constexpr int kXPlane = kMT * kKT;                 // halves per activation plane
 constexpr int kWPlane = kCout * kKT;               // halves per weight plane
 constexpr int kBufHalves = 2 * kXPlane + 2 * kWPlane;
 static_assert(2 * kBufHalves * 2 <= kLdsBytesPerCU, "LDS budget");
-
-// [row][32 halves] images (64-B rows); the 16-byte chunk index is XOR-swizzled with row bits 1..2 so that
-// the fragment reads (16 rows x 4 chunks per 64 lanes) and the tile writes spread over all banks.
-__device__ inline int swz(int row, int chunk) { return row * kKT + ((chunk ^ ((row >> 1) & 3)) << 3); }
 
 template <bool B>
 struct Flag {

@@ -11,7 +11,7 @@
 // The 8 waves are (MT / 128) x (C / 32): a wave owns 128 pixels (8 tiles of 16, from pixel offset `pix`) x 32 channels (2 tiles of 16,
 // wave column `wcol`): acc[8][2] / accx[8][2].
 //
-// Why the bits equal those of the per-tap kernels (conv3x3_wreg of csrc/conv3x3.hip, conv_split_pre of csrc/conv_split.hip):
+// Why the bits equal those of the per-tap kernels (conv3x3_wreg of csrc/conv3x3.hip, conv_split's split-input instances of csrc/conv_split.hip):
 //   * steps run in (tap 0..8, channel block 0..C/32-1) order; per step and pixel tile Ah*Wh into acc, then Ah*Wl, then Al*Wh into
 //     accx: every accumulator sees the same operands in the same order, whatever the wave layout;
 //   * the weight fragments go straight from the pack into two alternating register sets, one step ahead, no weight LDS;
@@ -35,48 +35,18 @@
 
 #include <mutex>
 
-#include "common.h"
+#include "split_f16.h"      // the vector types, kKT, kThreads, the activation scale, split4, overlap
 
 namespace rmnet {
 namespace {
 
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef _Float16 half4 __attribute__((ext_vector_type(4)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));   // 16 bytes of packed halves (native vector: see conv3x3.hip)
-
-constexpr int kKT = 32;          // K per step (one tap x 32 input channels)
-constexpr int kThreads = 512;
-constexpr float kActScale = 64.0f;                 // 2^6
-constexpr float kActUnscale = 1.0f / 64.0f;
-constexpr float kF16Max = 65504.0f;
-constexpr int kZeroRows = 4;                       // rows of zeros behind the staged ones: 256 B, one 16-byte slot for every slot of a bank row
+constexpr int kZeroRows = 4;                      // rows of zeros behind the staged ones: 256 B, one 16-byte slot for every slot of a bank row
 constexpr int kAhead = 1;                          // pixel tiles that the fragment reads run ahead of their MFMAs (2 and 3: the same time)
 
 constexpr int rows_image_bytes(int C, int MT) { return (MT + 2 + kZeroRows) * C * 4; }
 
 // halves from the start of a plane to 16-byte chunk `chunk` of row `row`
 __device__ inline int swzr(int row, int chunk) { return row * kKT + ((chunk ^ ((row >> 1) & 2)) << 3); }
-
-// The split of four activations: c = clamp(64 v), hi = fp16(c), lo = fp16(c - hi); an element outside the fp16 window (NaN included:
-// it saturates to -65504) adds `count` to bad.
-__device__ inline void split4(const f32x4 v, half4& hi, half4& lo, int& bad, int count = 1) {
-#pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    const float y = v[e] * kActScale;
-    bad += !(fabsf(y) <= kF16Max) ? count : 0;
-    const float c = fminf(fmaxf(y, -kF16Max), kF16Max);
-    const _Float16 h = (_Float16)c;
-    hi[e] = h;
-    lo[e] = (_Float16)(c - (float)h);
-  }
-}
-
-inline bool overlap(const void* p, long long pn, const void* q, long long qn) {
-  const char* a = reinterpret_cast<const char*>(p);
-  const char* b = reinterpret_cast<const char*>(q);
-  return a < b + qn && b < a + pn;
-}
 
 extern __shared__ __attribute__((aligned(16))) _Float16 rows_lds[];      // rows_image_bytes(C, MT), sized at launch
 

@@ -24,35 +24,45 @@
 // One LDS double buffer (X hi/lo [MT][32] + W hi/lo [NT][32] fp16), one barrier per K step, as in conv3x3.hip.  The next step's
 // operands are prefetched into VGPRs (native vector types: an array of HIP's uint4 would be placed in LDS) while the MFMAs run.
 //
-// conv_split_pre, further down, is a COPY of conv_split (loader, mma, epilogue) that reads and / or writes the split activation form;
-// conv_split's code object is kept as it is, so the two are kept in step by hand: a change to the arithmetic, the K order or the
-// epilogue expressions of one belongs in the other, and tests/test_conv_presplit.py compares them bit for bit.
-#include "conv_rows_core.h"      // the split-fp16 vocabulary (vector types, kKT, kThreads, the activation scale), split4, overlap
+// One kernel template, conv_split<WM, WN, TI, TJ, WPE, XS, OS>, serves the fp32 tensors and the split ACTIVATION form
+// (include/rmnet_hip.h): [M][C / 32][2][32] fp16 -- per pixel and block of 32 channels the 32 hi halves, then the 32 lo halves, of
+// c = clamp(64 * pre(v)).  A pixel has the byte stride it has in fp32, and every 16-byte chunk is 8 halves of one plane: exactly a
+// chunk of the LDS image.  XS: the input is in that form; OS: the output is written in it.  Tiles, weight path, mma, K order and
+// the epilogue's arithmetic are common to the four (XS, OS) pairs; what differs stands in `if constexpr` branches:
+//   load_x / store_x   XS 0: a float4 per item (thread = pixel tid / 8 + 64 i, channels 4 (tid % 8) ..), ReLU, split4 and the range
+//                            count at every tap and Cout slice that reads the element, two 8-byte LDS stores;
+//                      XS 1: a 16-byte load and a 16-byte LDS store per item (chunk tid % 8: plane tid % 8 / 4, channels
+//                            8 (tid % 4) ..); nothing is converted, clamped or counted (the producer did that, once per element);
+//   the K loop         XS 0, Mid only: the loads are taken "in turn" (see kInTurn); every other instance has all of a step's loads
+//                            in flight before its first MFMA;
+//   the store          OS 0: a lane's 4 channels as one float4, to out, or to out / out2 on either side of csplit;
+//                      OS 1: as 8 bytes of hi and 8 bytes of lo (split4), the elements outside the window counted here, once each.
+// 12 instances: 3 tiles x 4 pairs.  rmnet_conv_split_f32 is the (0, 0) pair alone, rmnet_conv_split_pre_f32 takes all four.
+#include "split_f16.h"      // the vector types, kKT, kThreads, the activation scale, swz, split4, overlap
 
 namespace rmnet {
 namespace {
 
-// [row][32 halves] images (64-B rows), 16-byte chunk index XOR-swizzled with row bits 1..2 (conv3x3.hip's layout)
-__device__ inline int swz(int row, int chunk) { return row * kKT + ((chunk ^ ((row >> 1) & 3)) << 3); }
-
 struct SplitArgs {
-  const float* x;          // [N][H][W][Cin]
+  const float* x;          // XS 0: [N][H][W][Cin] fp32
+  const _Float16* xs;      // XS 1: [N][H][W][Cin / 32][2][32] fp16
   const u32x4* wp;         // [k*k][Cin / 32][2][Cout][32] fp16
   const float* unscale;    // [Cout]
   const float* shift;      // [Cout] or null
-  const float* res;        // [M][Cout] or null
-  float* out;              // [M][Cout], or [M][csplit] with out2
-  float* out2;             // null, or [M][Cout - csplit]: channels csplit .. Cout-1
+  const float* res;        // [M][Cout] fp32 or null
+  float* out;              // OS 0: [M][Cout] fp32, or [M][csplit] with out2
+  float* out2;             // OS 0 only: null, or [M][Cout - csplit]: channels csplit .. Cout-1
+  _Float16* outs;          // OS 1: [M][Cout / 32][2][32] fp16
   int* range;              // or null
   int M, H, W, Ho, Wo, Cin, Cout, csplit, ksize, stride, pad, relu_in, relu_out;
 };
 
 // WPE: waves per SIMD the register allocation must allow -- 2 (one workgroup per CU) for Big, 4 (two) for Mid / Narrow
-template <int WM, int WN, int TI, int TJ, int WPE>
+template <int WM, int WN, int TI, int TJ, int WPE, bool XS, bool OS>
 __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(WPE))) void conv_split(SplitArgs a) {
   static_assert(WM * WN * 64 == kThreads, "8 waves");
   constexpr int MT = WM * TI * 16, NT = WN * TJ * 16;
-  constexpr int XI = MT / 64;                      // activation float4s per thread and step
+  constexpr int XI = MT / 64;                      // activation items per thread and step (16 bytes each, either form)
   constexpr int WI = NT / 64;                      // weight 16-byte chunks per thread and step
   constexpr int kXPlane = MT * kKT, kWPlane = NT * kKT;
   constexpr int kBufHalves = 2 * kXPlane + 2 * kWPlane;
@@ -65,7 +75,7 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(WPE)))
   const int CB = a.Cin / kKT, steps = a.ksize * a.ksize * CB;
   const int HWo = a.Ho * a.Wo;
 
-  // loader items: activations XI x float4 (pixel p = tid/8 + 64i, channels 4*(tid&7) ..), weights WI x 16 B
+  // loader items: activations XI x 16 bytes (pixel p = tid/8 + 64i; c4: see load_x / store_x in the header), weights WI x 16 B
   const int c4 = tid & 7;
   int pbase[XI], ph[XI], pw[XI];      // input pixel of tap (0, 0): flat index, row, column (outside the map: not read)
 #pragma unroll
@@ -74,276 +84,6 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(WPE)))
     const int n = m / HWo, r = m - n * HWo;
     const int ho = r / a.Wo, wo = r - ho * a.Wo;
     ph[i] = m < a.M ? ho * a.stride - a.pad : -4;       // (past M: every tap's row is < 0)
-    pw[i] = wo * a.stride - a.pad;
-    pbase[i] = (n * a.H + ph[i]) * a.W + pw[i];
-  }
-  f32x4 xr[XI];
-  u32x4 wr[WI];
-  int bad = 0;
-
-  auto load_x = [&](int s) {
-    const int tap = s / CB, cb = s - tap * CB;
-    const int ky = tap / a.ksize, kx = tap - ky * a.ksize;
-#pragma unroll
-    for (int i = 0; i < XI; ++i) {
-      const int h = ph[i] + ky, w = pw[i] + kx;
-      if ((unsigned)h < (unsigned)a.H && (unsigned)w < (unsigned)a.W) {
-        const size_t off = (size_t)(pbase[i] + ky * a.W + kx) * a.Cin + cb * kKT + 4 * c4;
-        xr[i] = *reinterpret_cast<const f32x4*>(a.x + off);
-      } else {
-        xr[i] = f32x4{0.f, 0.f, 0.f, 0.f};
-      }
-    }
-  };
-  auto load_w = [&](int s) {
-    const u32x4* wsrc = a.wp + (size_t)s * (a.Cout * 8);
-#pragma unroll
-    for (int i = 0; i < WI; ++i) {
-      const int q = tid + kThreads * i;
-      const int plane = q / (NT * 4), co = (q >> 2) % NT, ch = q & 3;
-      wr[i] = wsrc[plane * (a.Cout * 4) + (n0 + co) * 4 + ch];
-    }
-  };
-
-  auto counted = [&](int t) { return t == a.pad || (a.stride == 2 && a.ksize == 3 && t == 2); };
-
-  auto store_x = [&](int s, _Float16* buf) {
-    const int tap = s / CB, ky = tap / a.ksize, kx = tap - ky * a.ksize;
-    const bool count = blockIdx.y == 0 && counted(ky) && counted(kx);   // (every Cout slice reads the same inputs: count in one)
-    _Float16* xh = buf;
-    _Float16* xl = buf + kXPlane;
-#pragma unroll
-    for (int i = 0; i < XI; ++i) {
-      half4 hi, lo;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        float v = xr[i][e];
-        if (a.relu_in) v = v < 0.0f ? 0.0f : v;          // (keeps NaN: it is counted below)
-        const float y = v * kActScale;
-        bad += (count && !(fabsf(y) <= kF16Max)) ? 1 : 0;  // (the padding's zeros pass)
-        const float c = fminf(fmaxf(y, -kF16Max), kF16Max);
-        const _Float16 h = (_Float16)c;
-        hi[e] = h;
-        lo[e] = (_Float16)(c - (float)h);
-      }
-      const int p = (tid >> 3) + 64 * i;
-      const int o = swz(p, c4 >> 1) + 4 * (c4 & 1);
-      *reinterpret_cast<half4*>(xh + o) = hi;
-      *reinterpret_cast<half4*>(xl + o) = lo;
-    }
-  };
-  auto store_w = [&](_Float16* buf) {
-    _Float16* wb = buf + 2 * kXPlane;
-#pragma unroll
-    for (int i = 0; i < WI; ++i) {
-      const int q = tid + kThreads * i;
-      const int plane = q / (NT * 4), co = (q >> 2) % NT, ch = q & 3;
-      *reinterpret_cast<u32x4*>(wb + plane * kWPlane + swz(co, ch)) = wr[i];
-    }
-  };
-
-  f32x4 acc[TI][TJ], accx[TI][TJ];      // hi*hi, and the two cross terms apart
-#pragma unroll
-  for (int i = 0; i < TI; ++i)
-#pragma unroll
-    for (int j = 0; j < TJ; ++j) acc[i][j] = accx[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-  load_x(0);
-  load_w(0);
-  store_x(0, lds);
-  store_w(lds);
-  __syncthreads();
-  const int fr = lane & 15, fc = lane >> 4;
-  auto mma = [&](const _Float16* cur, auto&& halfway) {
-    const _Float16* xh = cur;
-    const _Float16* xl = cur + kXPlane;
-    const _Float16* wh = cur + 2 * kXPlane;
-    const _Float16* wl = wh + kWPlane;
-    if constexpr (TJ >= TI) {             // all activation fragments held, weight fragments streamed (Big)
-      half8 bh[TI], bl[TI];
-#pragma unroll
-      for (int i = 0; i < TI; ++i) {
-        const int o = swz(wm * TI * 16 + i * 16 + fr, fc);
-        bh[i] = *reinterpret_cast<const half8*>(xh + o);
-        bl[i] = *reinterpret_cast<const half8*>(xl + o);
-      }
-#pragma unroll
-      for (int j = 0; j < TJ; ++j) {
-        const int o = swz(wn * TJ * 16 + j * 16 + fr, fc);
-        const half8 ah = *reinterpret_cast<const half8*>(wh + o);
-        const half8 al = *reinterpret_cast<const half8*>(wl + o);
-#pragma unroll
-        for (int i = 0; i < TI; ++i) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bh[i], acc[i][j], 0, 0, 0);
-#pragma unroll
-        for (int i = 0; i < TI; ++i) accx[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bl[i], accx[i][j], 0, 0, 0);
-#pragma unroll
-        for (int i = 0; i < TI; ++i) accx[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(al, bh[i], accx[i][j], 0, 0, 0);
-        if (j == TJ / 2 - 1) halfway();
-      }
-    } else {                              // the other way round (Mid, Narrow): 24 fragment VGPRs instead of 40, inside 128
-      half8 ah[TJ], al[TJ];
-#pragma unroll
-      for (int j = 0; j < TJ; ++j) {
-        const int o = swz(wn * TJ * 16 + j * 16 + fr, fc);
-        ah[j] = *reinterpret_cast<const half8*>(wh + o);
-        al[j] = *reinterpret_cast<const half8*>(wl + o);
-      }
-#pragma unroll
-      for (int i = 0; i < TI; ++i) {
-        const int o = swz(wm * TI * 16 + i * 16 + fr, fc);
-        const half8 bh = *reinterpret_cast<const half8*>(xh + o);
-        const half8 bl = *reinterpret_cast<const half8*>(xl + o);
-#pragma unroll
-        for (int j = 0; j < TJ; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[j], bh, acc[i][j], 0, 0, 0);
-#pragma unroll
-        for (int j = 0; j < TJ; ++j) accx[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[j], bl, accx[i][j], 0, 0, 0);
-#pragma unroll
-        for (int j = 0; j < TJ; ++j) accx[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(al[j], bh, accx[i][j], 0, 0, 0);
-        if (i == TI / 2 - 1) halfway();
-      }
-    }
-  };
-  // The last step is apart, so that the loop body has no branch around the loads and the stores (see conv3x3.hip).  Big and
-  // Narrow: all of a step's global loads are in flight before its first MFMA, and nothing that waits for them is moved in among
-  // the MFMAs.  Mid cannot hold 8 VGPRs of activations and 8 of weights in flight next to its fragments inside 128 VGPRs, so it
-  // takes them in turn: the activations fly during the first half of the MFMAs and are split and stored half way (the other
-  // buffer is free from the last barrier on), the weights fly during the second half.
-  constexpr bool kInTurn = TI > TJ && WPE == 4 && WI > 1;
-  for (int s = 0; s + 1 < steps; ++s) {
-    _Float16* nxt = lds + ((s + 1) & 1) * kBufHalves;
-    load_x(s + 1);
-    if constexpr (!kInTurn) load_w(s + 1);
-    __builtin_amdgcn_sched_barrier(0);
-    mma(lds + (s & 1) * kBufHalves, [&] {
-      if constexpr (kInTurn) {
-        __builtin_amdgcn_sched_barrier(0);
-        load_w(s + 1);
-        store_x(s + 1, nxt);
-        __builtin_amdgcn_sched_barrier(0);
-      }
-    });
-    __builtin_amdgcn_sched_barrier(0);
-    if constexpr (!kInTurn) store_x(s + 1, nxt);
-    store_w(nxt);
-    __syncthreads();
-  }
-  mma(lds + ((steps - 1) & 1) * kBufHalves, [] {});
-
-  // epilogue: D[co][px] -- lane holds pixel fr of each 16-pixel tile and channels 4*fc .. 4*fc+3 of each 16-channel tile.
-  // The residual: out may BE res, so the compiler keeps every read of res in front of the stores that follow it in the source.
-  // All TI x TJ reads are therefore issued here, before the first store (one round trip, not TI x TJ dependent ones; the loader's
-  // registers are dead by now).  This is safe with out == res: a thread reads exactly the elements it later writes, and no other
-  // thread touches them.
-  f32x4 r[TI][TJ];
-  if (a.res) {
-#pragma unroll
-    for (int i = 0; i < TI; ++i) {
-      const int m = m0 + wm * TI * 16 + i * 16 + fr;
-#pragma unroll
-      for (int j = 0; j < TJ; ++j) {
-        const int co = n0 + wn * TJ * 16 + j * 16 + 4 * fc;
-        r[i][j] = m < a.M ? *reinterpret_cast<const f32x4*>(a.res + (size_t)m * a.Cout + co) : f32x4{0.f, 0.f, 0.f, 0.f};
-      }
-    }
-  }
-  // Unscale and shift in place, for all tiles, before the first store: for all the compiler knows these vectors alias out too, and
-  // read between the stores they would cost one more waited-for round trip per channel tile.
-#pragma unroll
-  for (int j = 0; j < TJ; ++j) {
-    const int co = n0 + wn * TJ * 16 + j * 16 + 4 * fc;
-    const f32x4 us = *reinterpret_cast<const f32x4*>(a.unscale + co) * kActUnscale;
-    const f32x4 b = a.shift ? *reinterpret_cast<const f32x4*>(a.shift + co) : f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int i = 0; i < TI; ++i) acc[i][j] = (acc[i][j] + accx[i][j]) * us + b;
-  }
-  // (An empty statement the optimiser cannot see through: without it the loop above is sunk into the guarded stores below, and
-  // each tile's wait for its unscale vector then includes the stores issued before it.)
-#pragma unroll
-  for (int j = 0; j < TJ; ++j)
-#pragma unroll
-    for (int i = 0; i < TI; ++i) asm volatile("" : "+v"(acc[i][j]));
-#pragma unroll
-  for (int j = 0; j < TJ; ++j) {
-    const int co = n0 + wn * TJ * 16 + j * 16 + 4 * fc;
-#pragma unroll
-    for (int i = 0; i < TI; ++i) {
-      const int m = m0 + wm * TI * 16 + i * 16 + fr;
-      if (m >= a.M) continue;
-      const size_t off = (size_t)m * a.Cout + co;
-      f32x4 v = acc[i][j];
-      if (a.res) v += r[i][j];
-      if (a.relu_out) {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] = v[e] < 0.0f ? 0.0f : v[e];
-      }
-      if (!a.out2)
-        *reinterpret_cast<f32x4*>(a.out + off) = v;
-      else if (co < a.csplit)         // (csplit % 4 == 0: a lane's 4 channels fall on one side)
-        *reinterpret_cast<f32x4*>(a.out + (size_t)m * a.csplit + co) = v;
-      else
-        *reinterpret_cast<f32x4*>(a.out2 + (size_t)m * (a.Cout - a.csplit) + (co - a.csplit)) = v;
-    }
-  }
-  if (a.range && bad) atomicAdd(a.range, bad);
-}
-
-template <int WM, int WN, int TI, int TJ, int WPE>
-void launch(const SplitArgs& a, hipStream_t st) {
-  constexpr int MT = WM * TI * 16, NT = WN * TJ * 16;
-  hipLaunchKernelGGL((conv_split<WM, WN, TI, TJ, WPE>), dim3((unsigned)((a.M + MT - 1) / MT), (unsigned)(a.Cout / NT)), dim3(kThreads),
-                     0, st, a);
-}
-
-// ------------------------------------------------------------------------------------------------ pre-split activations
-// The split ACTIVATION form (include/rmnet_hip.h): [M][C / 32][2][32] fp16 -- per pixel and block of 32 channels the 32 hi halves,
-// then the 32 lo halves, of c = clamp(64 * pre(v)).  A pixel has the byte stride it has in fp32, and every 16-byte chunk is 8 halves of
-// one plane: exactly a chunk of the LDS image.  split4 (csrc/conv_rows_core.h) is store_x's per-element arithmetic, expression for
-// expression.
-struct PreArgs {
-  const float* x;          // XS 0: [N][H][W][Cin] fp32
-  const _Float16* xs;      // XS 1: [N][H][W][Cin / 32][2][32] fp16
-  const u32x4* wp;
-  const float* unscale;
-  const float* shift;
-  const float* res;        // [M][Cout] fp32 or null
-  float* out;              // OS 0: [M][Cout] fp32, or [M][csplit] with out2
-  float* out2;             // OS 0 only
-  _Float16* outs;          // OS 1: [M][Cout / 32][2][32] fp16
-  int* range;
-  int M, H, W, Ho, Wo, Cin, Cout, csplit, ksize, stride, pad, relu_in, relu_out;
-};
-
-// conv_split with the activations read from the split form (XS) and / or the output written in it (OS); tiles, mma, K order and
-// epilogue expressions are conv_split's.  XS: the loader is a 16-byte load and a 16-byte LDS store per item (thread = pixel
-// tid / 8 + 64 i, chunk tid % 8: plane tid % 8 / 4, channels 8 (tid % 4) ..), nothing is converted, clamped or counted in the loop
-// (the producer did that, once per element), and every tile has all of a step's loads in flight before its first MFMA.  XS 0 keeps
-// store_x's loop, Mid's "in turn" form included.  OS: a lane's 4 channels go out as 8 bytes of hi and 8 bytes of lo, and the
-// elements outside the window are counted here, once each.
-template <int WM, int WN, int TI, int TJ, int WPE, bool XS, bool OS>
-__global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(WPE))) void conv_split_pre(PreArgs a) {
-  static_assert(WM * WN * 64 == kThreads, "8 waves");
-  constexpr int MT = WM * TI * 16, NT = WN * TJ * 16;
-  constexpr int XI = MT / 64;                      // activation items per thread and step (16 bytes each, either form)
-  constexpr int WI = NT / 64;
-  constexpr int kXPlane = MT * kKT, kWPlane = NT * kKT;
-  constexpr int kBufHalves = 2 * kXPlane + 2 * kWPlane;
-  static_assert(2 * kBufHalves * 2 <= kLdsBytesPerCU, "LDS budget");
-  __shared__ __attribute__((aligned(16))) _Float16 lds[2 * kBufHalves];
-
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int wm = wave % WM, wn = wave / WM;
-  const int m0 = blockIdx.x * MT, n0 = blockIdx.y * NT;
-  const int CB = a.Cin / kKT, steps = a.ksize * a.ksize * CB;
-  const int HWo = a.Ho * a.Wo;
-
-  const int c4 = tid & 7;
-  int pbase[XI], ph[XI], pw[XI];
-#pragma unroll
-  for (int i = 0; i < XI; ++i) {
-    const int m = m0 + (tid >> 3) + 64 * i;
-    const int n = m / HWo, r = m - n * HWo;
-    const int ho = r / a.Wo, wo = r - ho * a.Wo;
-    ph[i] = m < a.M ? ho * a.stride - a.pad : -4;
     pw[i] = wo * a.stride - a.pad;
     pbase[i] = (n * a.H + ph[i]) * a.W + pw[i];
   }
@@ -398,18 +138,20 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(WPE)))
       }
     } else {
       const int tap = s / CB, ky = tap / a.ksize, kx = tap - ky * a.ksize;
-      const bool count = blockIdx.y == 0 && counted(ky) && counted(kx);
+      const bool count = blockIdx.y == 0 && counted(ky) && counted(kx);   // (every Cout slice reads the same inputs: count in one)
       _Float16* xh = buf;
       _Float16* xl = buf + kXPlane;
 #pragma unroll
       for (int i = 0; i < XI; ++i) {
+        // split4's arithmetic, element for element, written out: with a call of split4(v, hi, lo, bad, count) here the compiler gives
+        // the fp32-input instances other code (Mid: 128 VGPRs instead of 126, 21 more instructions)
         half4 hi, lo;
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
           float v = xr[i][e];
-          if (a.relu_in) v = v < 0.0f ? 0.0f : v;
+          if (a.relu_in) v = v < 0.0f ? 0.0f : v;          // (keeps NaN: it is counted below)
           const float y = v * kActScale;
-          bad += (count && !(fabsf(y) <= kF16Max)) ? 1 : 0;
+          bad += (count && !(fabsf(y) <= kF16Max)) ? 1 : 0;  // (the padding's zeros pass)
           const float c = fminf(fmaxf(y, -kF16Max), kF16Max);
           const _Float16 h = (_Float16)c;
           hi[e] = h;
@@ -432,7 +174,7 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(WPE)))
     }
   };
 
-  f32x4 acc[TI][TJ], accx[TI][TJ];
+  f32x4 acc[TI][TJ], accx[TI][TJ];      // hi*hi, and the two cross terms apart
 #pragma unroll
   for (int i = 0; i < TI; ++i)
 #pragma unroll
@@ -444,14 +186,14 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(WPE)))
   store_w(lds);
   __syncthreads();
   const int fr = lane & 15, fc = lane >> 4;
-  // conv_split's mma, term for term.  A fragment's swizzle depends on its row's bits 1..2 alone, which a step of 16 rows leaves
-  // alone: one address per operand (xo, wo) and constant offsets from it, instead of one address register per fragment
+  // A fragment's swizzle depends on its row's bits 1..2 alone, which a step of 16 rows leaves alone: one address per operand
+  // (xo, wo) and constant offsets from it, instead of one address register per fragment
   const int xo = swz(wm * TI * 16 + fr, fc), wo = 2 * kXPlane + swz(wn * TJ * 16 + fr, fc);
   constexpr int kFrag = 16 * kKT;
   auto mma = [&](const _Float16* cur, auto&& halfway) {
     const _Float16* xb = cur + xo;
     const _Float16* wb = cur + wo;
-    if constexpr (TJ >= TI) {
+    if constexpr (TJ >= TI) {             // all activation fragments held, weight fragments streamed (Big)
       half8 bh[TI], bl[TI];
 #pragma unroll
       for (int i = 0; i < TI; ++i) {
@@ -470,7 +212,7 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(WPE)))
         for (int i = 0; i < TI; ++i) accx[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(al, bh[i], accx[i][j], 0, 0, 0);
         if (j == TJ / 2 - 1) halfway();
       }
-    } else {
+    } else {                              // the other way round (Mid, Narrow): 24 fragment VGPRs instead of 40, inside 128
       half8 ah[TJ], al[TJ];
 #pragma unroll
       for (int j = 0; j < TJ; ++j) {
@@ -491,7 +233,12 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(WPE)))
       }
     }
   };
-  // XS: 16 VGPRs of loads in flight (Mid) and nothing to convert, so no tile takes its loads in turn
+  // The last step is apart, so that the loop body has no branch around the loads and the stores (see conv3x3.hip).  All of a step's
+  // global loads are in flight before its first MFMA, and nothing that waits for them is moved in among the MFMAs -- except in
+  // Mid with fp32 input, which cannot hold 8 VGPRs of activations and 8 of weights in flight next to its fragments inside 128 VGPRs,
+  // so it takes them in turn: the activations fly during the first half of the MFMAs and are split and stored half way (the other
+  // buffer is free from the last barrier on), the weights fly during the second half.  With a split input Mid has 16 VGPRs of loads
+  // in flight and nothing to convert, so no tile takes its loads in turn.
   constexpr bool kInTurn = !XS && TI > TJ && WPE == 4 && WI > 1;
   for (int s = 0; s + 1 < steps; ++s) {
     _Float16* nxt = lds + ((s + 1) & 1) * kBufHalves;
@@ -513,7 +260,11 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(WPE)))
   }
   mma(lds + ((steps - 1) & 1) * kBufHalves, [] {});
 
-  // epilogue: conv_split's (see there for the order of the reads and the empty statement); a split output never is res
+  // epilogue: D[co][px] -- lane holds pixel fr of each 16-pixel tile and channels 4*fc .. 4*fc+3 of each 16-channel tile.
+  // The residual: an fp32 out may BE res (a split one never is), so the compiler keeps every read of res in front of the stores that
+  // follow it in the source.  All TI x TJ reads are therefore issued here, before the first store (one round trip, not TI x TJ
+  // dependent ones; the loader's registers are dead by now).  This is safe with out == res: a thread reads exactly the elements it
+  // later writes, and no other thread touches them.
   f32x4 r[TI][TJ];
   if (a.res) {
 #pragma unroll
@@ -526,6 +277,8 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(WPE)))
       }
     }
   }
+  // Unscale and shift in place, for all tiles, before the first store: for all the compiler knows these vectors alias out too, and
+  // read between the stores they would cost one more waited-for round trip per channel tile.
 #pragma unroll
   for (int j = 0; j < TJ; ++j) {
     const int co = n0 + wn * TJ * 16 + j * 16 + 4 * fc;
@@ -534,6 +287,8 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(WPE)))
 #pragma unroll
     for (int i = 0; i < TI; ++i) acc[i][j] = (acc[i][j] + accx[i][j]) * us + b;
   }
+  // (An empty statement the optimiser cannot see through: without it the loop above is sunk into the guarded stores below, and
+  // each tile's wait for its unscale vector then includes the stores issued before it.)
 #pragma unroll
   for (int j = 0; j < TJ; ++j)
 #pragma unroll
@@ -561,7 +316,7 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(WPE)))
         const size_t off = (size_t)m * a.Cout + co;
         if (!a.out2)
           *reinterpret_cast<f32x4*>(a.out + off) = v;
-        else if (co < a.csplit)
+        else if (co < a.csplit)         // (csplit % 4 == 0: a lane's 4 channels fall on one side)
           *reinterpret_cast<f32x4*>(a.out + (size_t)m * a.csplit + co) = v;
         else
           *reinterpret_cast<f32x4*>(a.out2 + (size_t)m * (a.Cout - a.csplit) + (co - a.csplit)) = v;
@@ -572,20 +327,20 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(WPE)))
 }
 
 template <int WM, int WN, int TI, int TJ, int WPE, bool XS, bool OS>
-void launch_pre(const PreArgs& a, hipStream_t st) {
+void launch(const SplitArgs& a, hipStream_t st) {
   constexpr int MT = WM * TI * 16, NT = WN * TJ * 16;
-  hipLaunchKernelGGL((conv_split_pre<WM, WN, TI, TJ, WPE, XS, OS>), dim3((unsigned)((a.M + MT - 1) / MT), (unsigned)(a.Cout / NT)),
+  hipLaunchKernelGGL((conv_split<WM, WN, TI, TJ, WPE, XS, OS>), dim3((unsigned)((a.M + MT - 1) / MT), (unsigned)(a.Cout / NT)),
                      dim3(kThreads), 0, st, a);
 }
 
 template <bool XS, bool OS>
-void launch_pre_tile(const PreArgs& a, hipStream_t st) {      // rmnet_conv_split_f32's choice of tile
+void launch_tile(const SplitArgs& a, hipStream_t st) {      // the choice of tile (see the header)
   if (a.Cout % 256 == 0 && (long long)((a.M + 127) / 128) * (a.Cout / 256) >= 512)
-    launch_pre<2, 4, 4, 4, 2, XS, OS>(a, st);
+    launch<2, 4, 4, 4, 2, XS, OS>(a, st);     // Big    128 x 256
   else if (a.Cout % 128 == 0)
-    launch_pre<2, 4, 4, 2, 4, XS, OS>(a, st);
+    launch<2, 4, 4, 2, 4, XS, OS>(a, st);     // Mid    128 x 128
   else
-    launch_pre<4, 2, 2, 2, 4, XS, OS>(a, st);
+    launch<4, 2, 2, 2, 4, XS, OS>(a, st);     // Narrow 128 x 64
 }
 
 // fp32 NHWC -> split form, one item = 8 channels of one block: 32 bytes in, 16 bytes of hi and 16 of lo out.  No LDS.
@@ -619,64 +374,14 @@ __global__ __launch_bounds__(kSplitActThreads) void split_act(const float* __res
   if (range && bad) atomicAdd(range, bad);
 }
 
-}  // namespace
-}  // namespace rmnet
-
-extern "C" int rmnet_conv_split_f32(const float* x, const void* wpack, const float* w_unscale, const float* shift,
-                                    const float* res, int flags, int N, int H, int W, int Cin, int Cout, int ksize, int stride,
-                                    float* out, float* out2, int out_split, int32_t* range_word, void* stream) {
-  using namespace rmnet;
+// The argument rules and the launch of both entries.  `allowed`: the flag bits the entry takes.  Everything that is an invalid
+// argument is decided before anything that is unsupported, except the overlaps, which need the sizes.
+int conv_split_entry(const void* x, const void* wpack, const float* w_unscale, const float* shift, const float* res, int flags, int allowed,
+                     int N, int H, int W, int Cin, int Cout, int ksize, int stride, void* out, float* out2, int out_split,
+                     int32_t* range_word, void* stream) {
   if (!x || !wpack || !w_unscale || !out || N <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0) return RMNET_E_INVALID_ARG;
-  if (flags & ~(RMNET_CONV_RELU_IN | RMNET_CONV_RELU_OUT)) return RMNET_E_INVALID_ARG;
-  if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(wpack) | reinterpret_cast<uintptr_t>(w_unscale) |
-       reinterpret_cast<uintptr_t>(shift) | reinterpret_cast<uintptr_t>(res) | reinterpret_cast<uintptr_t>(out) |
-       reinterpret_cast<uintptr_t>(out2)) & 15)
-    return RMNET_E_INVALID_ARG;
-  if (out2 && (res || out_split <= 0 || out_split >= Cout || out_split % 4)) return RMNET_E_INVALID_ARG;
-  if ((ksize != 1 && ksize != 3) || (stride != 1 && stride != 2)) return RMNET_E_UNSUPPORTED;
-  if (Cin % kKT || Cout % 64) return RMNET_E_UNSUPPORTED;
-  const int pad = ksize / 2;
-  const int Ho = (H + 2 * pad - ksize) / stride + 1, Wo = (W + 2 * pad - ksize) / stride + 1;
-  const long long Mi = (long long)N * H * W, M = (long long)N * Ho * Wo;
-  if (Mi * Cin >= (1LL << 31) || M * Cout >= (1LL << 31)) return RMNET_E_UNSUPPORTED;   // (int pixel index, size_t offsets)
-  // out must not overlap x (other workgroups read the same input pixels); it may BE res: each element is read, then written, by
-  // one thread.  The epilogue reads all of a thread's residual values before its first store; a thread reads exactly the elements
-  // it later writes and no other thread touches them, so that is safe as well
-  const char* xb = reinterpret_cast<const char*>(x);
-  const char* ob = reinterpret_cast<const char*>(out);
-  const long long c1 = out2 ? out_split : Cout;
-  if (ob < xb + Mi * Cin * sizeof(float) && xb < ob + M * c1 * sizeof(float)) return RMNET_E_INVALID_ARG;
-  if (out2) {
-    const char* o2 = reinterpret_cast<const char*>(out2);
-    if (o2 < xb + Mi * Cin * sizeof(float) && xb < o2 + M * (Cout - c1) * sizeof(float)) return RMNET_E_INVALID_ARG;
-    if (o2 < ob + M * c1 * sizeof(float) && ob < o2 + M * (Cout - c1) * sizeof(float)) return RMNET_E_INVALID_ARG;
-  }
-  SplitArgs a;
-  a.x = x; a.wp = reinterpret_cast<const u32x4*>(wpack); a.unscale = w_unscale; a.shift = shift; a.res = res; a.out = out; a.out2 = out2;
-  a.range = range_word; a.M = (int)M; a.H = H; a.W = W; a.Ho = Ho; a.Wo = Wo; a.Cin = Cin; a.Cout = Cout; a.csplit = (int)c1;
-  a.ksize = ksize; a.stride = stride; a.pad = pad;
-  a.relu_in = (flags & RMNET_CONV_RELU_IN) != 0;
-  a.relu_out = (flags & RMNET_CONV_RELU_OUT) != 0;
-  hipStream_t st = (hipStream_t)stream;
-  if (Cout % 256 == 0 && (M + 127) / 128 * (Cout / 256) >= 512)
-    launch<2, 4, 4, 4, 2>(a, st);     // Big    128 x 256
-  else if (Cout % 128 == 0)
-    launch<2, 4, 4, 2, 4>(a, st);     // Mid    128 x 128
-  else
-    launch<4, 2, 2, 2, 4>(a, st);     // Narrow 128 x 64
-  return check_launch();
-}
-
-extern "C" int rmnet_conv_split_pre_f32(const void* x, const void* wpack, const float* w_unscale, const float* shift, const float* res,
-                                        int flags, int N, int H, int W, int Cin, int Cout, int ksize, int stride, void* out, float* out2,
-                                        int out_split, int32_t* range_word, void* stream) {
-  using namespace rmnet;
-  if (flags & ~(RMNET_CONV_RELU_IN | RMNET_CONV_RELU_OUT | RMNET_CONV_X_SPLIT | RMNET_CONV_OUT_SPLIT)) return RMNET_E_INVALID_ARG;
+  if (flags & ~allowed) return RMNET_E_INVALID_ARG;
   const bool xs = (flags & RMNET_CONV_X_SPLIT) != 0, os = (flags & RMNET_CONV_OUT_SPLIT) != 0;
-  if (!xs && !os)           // fp32 in, fp32 out: the kernel that has always served it
-    return rmnet_conv_split_f32(reinterpret_cast<const float*>(x), wpack, w_unscale, shift, res, flags, N, H, W, Cin, Cout, ksize, stride,
-                                reinterpret_cast<float*>(out), out2, out_split, range_word, stream);
-  if (!x || !wpack || !w_unscale || !out || N <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0) return RMNET_E_INVALID_ARG;
   if (xs && (flags & RMNET_CONV_RELU_IN)) return RMNET_E_INVALID_ARG;      // (the producer of a split tensor applies it)
   if (os && out2) return RMNET_E_INVALID_ARG;
   if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(wpack) | reinterpret_cast<uintptr_t>(w_unscale) |
@@ -689,16 +394,18 @@ extern "C" int rmnet_conv_split_pre_f32(const void* x, const void* wpack, const 
   const int pad = ksize / 2;
   const int Ho = (H + 2 * pad - ksize) / stride + 1, Wo = (W + 2 * pad - ksize) / stride + 1;
   const long long Mi = (long long)N * H * W, M = (long long)N * Ho * Wo;
-  if (Mi * Cin >= (1LL << 31) || M * Cout >= (1LL << 31)) return RMNET_E_UNSUPPORTED;
-  // either form has 4 bytes per element.  No output may overlap x; an fp32 out may BE res (conv_split's rule), a split one must not
-  // overlap it: its hi and lo chunks are not where the fp32 elements of the same channels are
+  if (Mi * Cin >= (1LL << 31) || M * Cout >= (1LL << 31)) return RMNET_E_UNSUPPORTED;   // (int pixel index, size_t offsets)
+  // Either form has 4 bytes per element.  No output may overlap x (other workgroups read the same input pixels).  An fp32 out may BE
+  // res: each element is read, then written, by one thread, and the epilogue's early reads are of exactly the elements that the
+  // thread later writes.  A split out must not overlap res: its hi and lo chunks are not where the fp32 elements of the same
+  // channels are
   const long long xbytes = Mi * Cin * 4, c1 = out2 ? out_split : Cout;
   if (overlap(out, M * c1 * 4, x, xbytes)) return RMNET_E_INVALID_ARG;
   if (os && res && overlap(out, M * c1 * 4, res, M * Cout * 4)) return RMNET_E_INVALID_ARG;
   if (out2) {
     if (overlap(out2, M * (Cout - c1) * 4, x, xbytes) || overlap(out2, M * (Cout - c1) * 4, out, M * c1 * 4)) return RMNET_E_INVALID_ARG;
   }
-  PreArgs a;
+  SplitArgs a;
   a.x = xs ? nullptr : reinterpret_cast<const float*>(x);
   a.xs = xs ? reinterpret_cast<const _Float16*>(x) : nullptr;
   a.wp = reinterpret_cast<const u32x4*>(wpack); a.unscale = w_unscale; a.shift = shift; a.res = res;
@@ -708,10 +415,29 @@ extern "C" int rmnet_conv_split_pre_f32(const void* x, const void* wpack, const 
   a.relu_in = (flags & RMNET_CONV_RELU_IN) != 0;
   a.relu_out = (flags & RMNET_CONV_RELU_OUT) != 0;
   hipStream_t st = (hipStream_t)stream;
-  if (xs && os) launch_pre_tile<true, true>(a, st);
-  else if (xs) launch_pre_tile<true, false>(a, st);
-  else launch_pre_tile<false, true>(a, st);
+  if (xs && os) launch_tile<true, true>(a, st);
+  else if (xs) launch_tile<true, false>(a, st);
+  else if (os) launch_tile<false, true>(a, st);
+  else launch_tile<false, false>(a, st);
   return check_launch();
+}
+
+}  // namespace
+}  // namespace rmnet
+
+extern "C" int rmnet_conv_split_f32(const float* x, const void* wpack, const float* w_unscale, const float* shift,
+                                    const float* res, int flags, int N, int H, int W, int Cin, int Cout, int ksize, int stride,
+                                    float* out, float* out2, int out_split, int32_t* range_word, void* stream) {
+  return rmnet::conv_split_entry(x, wpack, w_unscale, shift, res, flags, RMNET_CONV_RELU_IN | RMNET_CONV_RELU_OUT, N, H, W, Cin, Cout,
+                                 ksize, stride, out, out2, out_split, range_word, stream);
+}
+
+extern "C" int rmnet_conv_split_pre_f32(const void* x, const void* wpack, const float* w_unscale, const float* shift, const float* res,
+                                        int flags, int N, int H, int W, int Cin, int Cout, int ksize, int stride, void* out, float* out2,
+                                        int out_split, int32_t* range_word, void* stream) {
+  return rmnet::conv_split_entry(x, wpack, w_unscale, shift, res, flags,
+                                 RMNET_CONV_RELU_IN | RMNET_CONV_RELU_OUT | RMNET_CONV_X_SPLIT | RMNET_CONV_OUT_SPLIT, N, H, W, Cin, Cout,
+                                 ksize, stride, out, out2, out_split, range_word, stream);
 }
 
 extern "C" int rmnet_split_act_f32(const float* x, long long M, int C, int relu, void* out, int32_t* range_word, void* stream) {

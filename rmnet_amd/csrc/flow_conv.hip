@@ -31,24 +31,10 @@
 // [64][32] fp16: 48 KB) taken as DYNAMIC shared memory, one barrier per K step, the next step's operands prefetched into VGPRs
 // (native vector types) while the MFMAs run, the last step peeled, sched_barrier(0) around the MFMA block:
 // profiles/r12_a_weight_prefetch.md says why for each.
-#include "common.h"
+#include "split_f16.h"      // the vector types, kKT, kThreads, the activation scale, swz (conv3x3.hip's LDS layout)
 
 namespace rmnet {
 namespace {
-
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef _Float16 half4 __attribute__((ext_vector_type(4)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));   // 16 bytes of packed weights (native vector: see conv3x3.hip)
-
-constexpr int kKT = 32;          // K per step (one tap x 32 input channels)
-constexpr int kThreads = 512;
-constexpr float kActScale = 64.0f;                 // 2^6
-constexpr float kActUnscale = 1.0f / 64.0f;
-constexpr float kF16Max = 65504.0f;
-
-// [row][32 halves] images (64-B rows), 16-byte chunk index XOR-swizzled with row bits 1..2 (conv3x3.hip's layout)
-__device__ inline int swz(int row, int chunk) { return row * kKT + ((chunk ^ ((row >> 1) & 3)) << 3); }
 
 struct FlowArgs {
   const float* x;          // [N][H][W][x_ld]

@@ -21,7 +21,7 @@
 // workgroup whose 32 x 32 core (patch offset 3) holds it.
 // LDS: 81,920 B of pack + 32,856 B of patch planes + 512 B of epilogue constants (unscale / 64, bias) = 115,296 B, dynamic (prepared once per device: rows_prepare): one workgroup
 // (two waves per SIMD) per CU.  Measurements: profiles/r23_a_front_ends.md.
-#include "conv_rows_core.h"
+#include "conv_rows_core.h"      // rows_prepare; and through it split_f16.h: the vector types, kThreads, the activation scale, swz
 
 namespace rmnet {
 namespace {
@@ -50,8 +50,6 @@ static_assert(kTI * 8 == kCT && kThreads == 512, "eight waves, two conv rows eac
 static_assert((2 * (kCT - 1) * kPW + 2 * (kCT - 1)) * kCin + (kKReal - 1) + 6 * kRowSkip == kPatch - 1, "patch extent");
 
 extern __shared__ __attribute__((aligned(16))) _Float16 fs_lds[];      // kFlowStemLdsBytes, sized at launch
-
-__device__ inline int swz(int row, int chunk) { return row * 32 + ((chunk ^ ((row >> 1) & 3)) << 3); }
 
 struct FlowStemArgs {
   const float* img0;       // [N][3][H][W], frame n at img0 + n * bs0

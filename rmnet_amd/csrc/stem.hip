@@ -18,15 +18,11 @@
 // workgroup whose 32 x 32 core holds it, so the halo is not counted twice.
 // -Rpass-analysis=kernel-resource-usage: Cin 5: 208 VGPRs, 144,144 B of LDS; Cin 3: 202 VGPRs, 119,568 B; no spills, no scratch; one
 // workgroup (two waves per SIMD) per CU, by LDS.  Measurements: profiles/r09_a_stem_head.md.
-#include "common.h"
+#include "split_f16.h"      // the vector types, kThreads, the activation scale, swz
 
 namespace rmnet {
 namespace {
 
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-constexpr int kThreads = 512;
 constexpr int kCout = 64;
 constexpr int kPT = 8;                     // pooled tile edge
 constexpr int kCT = 2 * kPT + 1;           // conv tile edge (17)
@@ -36,11 +32,6 @@ constexpr int kM = kCT * kCT;              // 289 conv pixels
 constexpr int kMTiles = (kM + 15) / 16;    // 19
 constexpr int kTI = 3;                     // M tiles per wave (8 waves x 3 >= 19)
 constexpr int kCtStride = kCout + 4;       // conv tile row in LDS, padded: 16 pixel rows spread over the banks
-constexpr float kActScale = 64.0f;
-constexpr float kActUnscale = 1.0f / 64.0f;
-constexpr float kF16Max = 65504.0f;
-
-__device__ inline int swz(int row, int chunk) { return row * 32 + ((chunk ^ ((row >> 1) & 3)) << 3); }
 
 struct StemArgs {
   const float* frame;      // [N][3][H][W]

@@ -1,5 +1,5 @@
 # -*- coding: utf-8 -*-
-"""Pre-split activations (include/rmnet_hip.h; csrc/conv_split.hip: conv_split_pre, split_act): a tensor that only split-fp16
+"""Pre-split activations (include/rmnet_hip.h; csrc/conv_split.hip: conv_split<tile, XS, OS>, split_act): a tensor that only split-fp16
 convolutions read is kept as fp16 hi / lo planes and split once, by its producer, instead of at every tap and Cout tile of its
 reader.  The split depends on the element alone, so everything here is bit for bit:
 
@@ -10,12 +10,14 @@ reader.  The split depends on the element alone, so everything here is bit for b
     3x3 / stride 2, with and without res and the output ReLU, randn inputs (all three product terms live); the key / value form
     with two outputs; one live tap at a time on an input with a different integer in every element, where a tap's zeros in the
     wrong plane or chunk show;
-  * the producer: the split output of either input form == restatement(the old kernel's fp32 output), range word == the count
-    (a shift of +-3000 on two channels puts them outside the window);
-  * the argument rules of the two new entries;
+  * the producer: the split output of either input form == restatement(the fp32 instance's output), range word == the count
+    (a shift of +-3000 on two channels puts them outside the window).  The fp32 in / fp32 out instance and the split ones are
+    instances of one kernel template that differ in the loader, the K loop's order of loads and the store; the fp32 instance's own
+    bits are anchored against float64 in tests/test_conv_edges.py and tests/test_conv_split.py;
+  * the argument rules of rmnet_conv_split_pre_f32 and rmnet_split_act_f32;
   * four bottlenecks and the key / value heads with RMNET_CONV_PRESPLIT on and off: equal outputs, and a range word that is
     non-zero in both settings when an intermediate leaves the window; one graph capture and replay of the stage;
-  * CPU: the restatement's round trip, and the new kernels' registers, spills, scratch and LDS from the code object's metadata."""
+  * CPU: the restatement's round trip, and the twelve instances' registers, spills, scratch and LDS from the code object's metadata."""
 
 import ctypes
 
@@ -105,21 +107,25 @@ VGPR_LIMIT = {'Big': 256, 'Mid': 128, 'Narrow': 128}
 
 
 def test_the_new_kernels_keep_their_registers_lds_and_have_no_spill_or_scratch(tmp_path):
-    """Compile-only, with tests/test_kernel_resources.py's compile step and metadata reader: every instance of conv_split_pre has no
-    spill and no scratch, at most 128 VGPRs for Mid and Narrow (two workgroups per CU) and 256 for Big, and static LDS exactly the
-    declared double buffer (96 / 64 / 48 KB); split_act has no LDS, scratch or spill."""
+    """Compile-only, with tests/test_kernel_resources.py's compile step and metadata reader: every instance of conv_split<tile, XS, OS>
+    (all four pairs of input and output form x 3 tiles) has no spill and no scratch, at most 128 VGPRs for Mid and Narrow (two
+    workgroups per CU) and 256 for Big, and static LDS exactly the declared double buffer (96 / 64 / 48 KB); these twelve are the
+    file's only convolution kernels (no five-parameter conv_split, no conv_split_pre kernel is left); split_act has no LDS, scratch
+    or spill."""
     import test_kernel_resources as KR
     found = KR._kernels(KR._compile('conv_split.hip', str(tmp_path / 'conv_split.s')))
-    for xs, os_ in ((1, 1), (1, 0), (0, 1)):                 # (the VGPR counts of record: profiles/r17_a_presplit.md)
+    for xs, os_ in ((1, 1), (1, 0), (0, 1), (0, 0)):         # (the VGPR counts of record: profiles/r27_a_conv_split_fold.md)
         for tile, (wm, wn, ti, tj, wpe) in KR.TILES.items():
-            k = KR._one(found, '14conv_split_preILi%dELi%dELi%dELi%dELi%dELb%dELb%dEE' % (wm, wn, ti, tj, wpe, xs, os_))
+            k = KR._one(found, '10conv_splitILi%dELi%dELi%dELi%dELi%dELb%dELb%dEEE' % (wm, wn, ti, tj, wpe, xs, os_))
             print('%-6s x split %d out split %d  LDS %6d  scratch %d  VGPRs %3d  spilled %d'
                   % (tile, xs, os_, k['group_segment_fixed_size'], k['private_segment_fixed_size'], k['vgpr_count'],
                      k['vgpr_spill_count']))
             assert k['group_segment_fixed_size'] == KR._double_buffer_bytes(wm * ti * 16, wn * tj * 16), (tile, k)
             assert k['private_segment_fixed_size'] == 0 and k['vgpr_spill_count'] == 0, (tile, k)
             assert k['vgpr_count'] <= VGPR_LIMIT[tile], (tile, k)
-    assert len([n for n in found if '14conv_split_preI' in n]) == 9
+    assert len([n for n in found if '10conv_splitI' in n]) == 12
+    old = [n for n in found if '14conv_split_pre' in n or ('10conv_splitI' in n and 'ELb' not in n)]
+    assert not old, old                                      # (a leftover copy: the old seven- or five-parameter kernel)
     k = KR._one(found, '9split_actE')
     assert k['group_segment_fixed_size'] == 0 and k['private_segment_fixed_size'] == 0 and k['vgpr_spill_count'] == 0, k
 
@@ -147,7 +153,7 @@ def test_split_act_equals_the_restatement_bit_for_bit(shape, c, relu):
 
 # ================================================================================================ consumer and producer, every tile
 def _case(tile, shape, cin, k, s):
-    """One shape on one tile, res and the output ReLU on and off: conv_split's three new forms against the old kernel's output."""
+    """One shape on one tile, res and the output ReLU on and off: conv_split's three split forms against the fp32 in / fp32 out instance's output."""
     from rmnet_amd import ops
     n, h, w = shape
     g = torch.Generator().manual_seed(100 * cin + 10 * k + s + h)
@@ -225,7 +231,7 @@ def test_key_value_form_with_two_outputs_reads_a_split_input():
 def test_one_live_tap_at_a_time_on_a_split_input_with_a_different_integer_in_every_element():
     """x = (flat NHWC index mod 2039) - 1019: 64 x is an fp16 number, so the lo plane is all zero and the hi plane holds a different
     value in (nearly) every element.  A tap's zeros, or its values, in the wrong plane, chunk or pixel give a wrong integer: the result
-    must be the old kernel's AND the float64 convolution (exact: tests/conv_ref.py, section 1)."""
+    must be the fp32-input instance's AND the float64 convolution (exact: tests/conv_ref.py, section 1)."""
     from rmnet_amd import ops
     n, h, w = MAP_A
     cin, cout = 96, 128

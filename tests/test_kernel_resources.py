@@ -67,7 +67,8 @@ def _one(kernels, fragment):
 
 # ------------------------------------------------------------------------------------------------ the split-fp16 convolutions
 KT = 32
-# (WM, WN, TI, TJ, WPE) of conv_split's three instances (csrc/conv_split.hip, the end of the entry), and what WPE allows
+# (WM, WN, TI, TJ, WPE) of conv_split's three tiles (csrc/conv_split.hip, launch_tile), and what WPE allows; each tile has four
+# instances <..., XS, OS>: here the fp32 in / fp32 out one (Lb0ELb0), all twelve in tests/test_conv_presplit.py
 TILES = {'Big': (2, 4, 4, 4, 2), 'Mid': (2, 4, 4, 2, 4), 'Narrow': (4, 2, 2, 2, 4)}
 
 
@@ -79,7 +80,7 @@ def _double_buffer_bytes(mt, nt):
 def _conv_kernels(kernels):
     out = {'conv3x3_split': (_one(kernels, '13conv3x3_splitE'), 128, 256, 256)}
     for tile, (wm, wn, ti, tj, wpe) in TILES.items():
-        k = _one(kernels, '10conv_splitILi%dELi%dELi%dELi%dELi%dEE' % (wm, wn, ti, tj, wpe))
+        k = _one(kernels, '10conv_splitILi%dELi%dELi%dELi%dELi%dELb0ELb0EEE' % (wm, wn, ti, tj, wpe))
         out[tile] = (k, wm * ti * 16, wn * tj * 16, 256 if wpe == 2 else 128)
     return out
 
