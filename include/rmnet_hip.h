@@ -597,6 +597,35 @@ int rmnet_argmax_labels_f32(const float *prob, int N, int K, int H, int W, uint8
 int rmnet_overlay_u8(const float *frames, const uint8_t *labels, int N, int H, int W, const double *mean, const double *std,
                      double alpha, int ignore_idx, uint8_t *out, int32_t *workspace, size_t workspace_bytes, void *stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * H1  Multi-scale and flipped inference around the network passes (additive exports, same ABI version; csrc/tta.hip).
+ * Replaces: the F.interpolate / torch.flip / torch.stack / torch.mean sequence of multi_scale_inference
+ *           (utils/helpers.py:44-78) and the torch.argmax that follows it (core/inference.py:62).
+ * Plain fp32, every product and sum rounded on its own.  The coordinate rule of one axis, axis(d, in, scale):
+ *     s = max(fl(fl(scale * fl(d + 0.5f)) - 0.5f), 0);  i0 = min((int)s, in - 1);  i1 = min(i0 + 1, in - 1);
+ *     l1 = fl(s - (float)i0);  l0 = fl(1 - l1)
+ * and the value is  fl( fl(l0y * fl(fl(l0x*A) + fl(l1x*B))) + fl(l1y * fl(fl(l0x*C) + fl(l1x*D))) )  with A, B, C, D at
+ * (i0y,i0x), (i0y,i1x), (i1y,i0x), (i1y,i1x): the formula torch's bilinear kernel is written from, align_corners=False.
+ *
+ * rmnet_resize_bilinear_f32: src [P,Hs,Ws] f32 -> dst [P,Hd,Wd] f32 with the scales as floats; for
+ *     F.interpolate(scale_factor=fs) pass (float)(1.0 / fs) for both and Hd = floor(double(Hs) * fs), Wd likewise.
+ *     flip != 0 writes column Wd - 1 - x: torch.flip(resized, dims=[-1]) in the same pass.  src and dst must not overlap.
+ * rmnet_tta_merge_f32: E sources, srcs[e] a device pointer to [N,K,hs[e],ws[e]] f32; srcs, hs, ws, flipped are HOST arrays of
+ *     E entries, copied into the launch.  Entry e is resized to (H, W) with the scales fl((float)hs[e] / (float)H) and
+ *     fl((float)ws[e] / (float)W) (torch's rule for size=); a flipped entry is read at column ws[e] - 1 - x (the entry
+ *     holds a mirrored clip).  acc = v_0, acc = fl(acc + v_e) in entry order, mean = fl(acc / (float)E), a true division.
+ *     mean [N,K,H,W] f32 is fully written.  labels [N,H,W] uint8 (NULL: not wanted) is the first index of the maximum of the
+ *     written means over K, byte for byte what rmnet_argmax_labels_f32 returns on mean.  No workspace, one launch.
+ * RMNET_E_INVALID_ARG for a NULL pointer (labels excepted), a size < 1, E outside 1 .. RMNET_TTA_MAX_ENTRIES, K outside
+ * 1 .. 255, a scale that is not finite and positive or a pointer not aligned to 4 bytes; RMNET_E_UNSUPPORTED for Hd or
+ * ceil(H / 4) above 65535, a source side above 2^24 or a source plane of 2^31 elements or more.
+ * ------------------------------------------------------------------------------------------- */
+#define RMNET_TTA_MAX_ENTRIES 8
+int rmnet_resize_bilinear_f32(const float *src, int P, int Hs, int Ws, int Hd, int Wd, float scale_h, float scale_w, int flip,
+                              float *dst, void *stream);
+int rmnet_tta_merge_f32(const float *const *srcs, const int *hs, const int *ws, const int *flipped, int E, int N, int K, int H,
+                        int W, float *mean, uint8_t *labels, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -8,6 +8,8 @@ Public surface (mirrors the reference's module paths):
     rmnet_amd.reg_att_map_generator    <-> extensions/reg_att_map_generator (+ the compiled module)
     rmnet_amd.flow_affine_transformation <-> the compiled CPython module of the same name
     rmnet_amd.helpers                  <-> utils/helpers.py (pad_divide_by, var_or_cuda, multi_scale_inference)
+    rmnet_amd.tta                      the resize and merge around the passes of multi_scale_inference (csrc/tta.hip);
+                                       inference.segment_video_tta is the mode itself
     rmnet_amd.ops                      torch-facing wrappers over the C ABI (include/rmnet_hip.h)
     rmnet_amd.dist                     per-video sharding over the GPUs of a node + RCCL gather
 

@@ -14,6 +14,7 @@ LIB_PATH = os.environ.get('RMNET_HIP_LIB') or os.path.join(_HERE, 'librmnet_hip.
 c_f32p = ctypes.c_void_p   # device pointers travel as integers
 c_i32p = ctypes.c_void_p
 c_f64p = ctypes.POINTER(ctypes.c_double)   # host arrays (mean / std of the clip I/O entries)
+c_hostp = ctypes.c_void_p                  # host arrays of any element type (the per-entry tables of rmnet_tta_merge_f32)
 
 # name -> (restype, argtypes); must list every symbol declared in include/rmnet_hip.h
 SIGNATURES = {
@@ -137,6 +138,12 @@ SIGNATURES = {
     'rmnet_overlay_u8': (ctypes.c_int, [
         c_f32p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_f64p, c_f64p, ctypes.c_double, ctypes.c_int,
         ctypes.c_void_p, c_i32p, ctypes.c_size_t, ctypes.c_void_p]),
+    'rmnet_resize_bilinear_f32': (ctypes.c_int, [
+        c_f32p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_float, ctypes.c_float, ctypes.c_int,
+        c_f32p, ctypes.c_void_p]),
+    'rmnet_tta_merge_f32': (ctypes.c_int, [
+        c_hostp, c_hostp, c_hostp, c_hostp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_f32p,
+        ctypes.c_void_p, ctypes.c_void_p]),
 }
 
 ABI_VERSION = 6

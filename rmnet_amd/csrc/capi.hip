@@ -265,4 +265,14 @@ int rmnet_overlay_u8(const float* frames, const uint8_t* labels, int N, int H, i
                         static_cast<hipStream_t>(stream));
 }
 
+int rmnet_resize_bilinear_f32(const float* src, int P, int Hs, int Ws, int Hd, int Wd, float scale_h, float scale_w, int flip,
+                              float* dst, void* stream) {
+  return launch_resize_bilinear(src, P, Hs, Ws, Hd, Wd, scale_h, scale_w, flip, dst, static_cast<hipStream_t>(stream));
+}
+
+int rmnet_tta_merge_f32(const float* const* srcs, const int* hs, const int* ws, const int* flipped, int E, int N, int K, int H,
+                        int W, float* mean, uint8_t* labels, void* stream) {
+  return launch_tta_merge(srcs, hs, ws, flipped, E, N, K, H, W, mean, labels, static_cast<hipStream_t>(stream));
+}
+
 }  // extern "C"

@@ -416,6 +416,12 @@ int launch_argmax_labels(const float* prob, int N, int K, int H, int W, uint8_t*
 int launch_overlay(const float* frames, const uint8_t* labels, int N, int H, int W, const double* mean, const double* std, double alpha,
                    int ignore_idx, uint8_t* out, int32_t* ws, size_t ws_bytes, hipStream_t st);
 
+// tta.hip
+int launch_resize_bilinear(const float* src, int P, int Hs, int Ws, int Hd, int Wd, float scale_h, float scale_w, int flip, float* dst,
+                           hipStream_t st);
+int launch_tta_merge(const float* const* srcs, const int* hs, const int* ws, const int* flipped, int E, int N, int K, int H, int W,
+                     float* mean, uint8_t* labels, hipStream_t st);
+
 inline int check_launch() { return hipGetLastError() == hipSuccess ? RMNET_OK : RMNET_E_LAUNCH; }
 
 }  // namespace rmnet

@@ -38,14 +38,72 @@ def segment_video(net, flownet, video, memorize_every=5):
     return est[0].argmax(dim=1).to(torch.uint8)
 
 
+# Whether segment_video_tta runs a scale's unflipped and flipped clips as one batch of two.  Measured on an MI355X on 70-frame 480p
+# clips, scales (0.75, 1.0, 1.25) + flip (profiles/r28_a_tta.md): paired 2.51 s against 2.99 s with one object, 5.50 s against 5.83 s with
+# three, the runs of a variant within 0.05 s of each other.
+PAIR_FLIPS = True
+
+
 @torch.no_grad()
-def segment_video_u8(net, flownet, frames_u8, labels_u8, n_max_objects, mean, std, memorize_every=5, overlay=True):
+def segment_video_tta(net, flownet, video, frame_scales=(1.0,), flip_lr=False, memorize_every=5, pair_flips=None):
+    """One clip at several scales, optionally also mirrored left-right, merged on the device: multi_scale_inference
+    (utils/helpers.py:44-78) followed by the driver's argmax.  ``video`` as for ``segment_video``.  Returns {'probs': float32
+    [N,K,H,W], 'labels': uint8 [N,H,W]} on the model's device.
+
+    Per scale: the frames are resized by ``tta.resize_bilinear``, the first frame's masks by nearest neighbour, TinyFlowNet runs once
+    on the unflipped frames, and the flipped twin takes the mirrored flow with its x channel negated, as the reference does.  With
+    ``pair_flips`` the two clips of a scale go through ONE ``net`` call as a batch of two (slot 1 holds the mirrored frames, written
+    by the resize itself); otherwise through two calls.  The entries -- per scale the unflipped, then the flipped one -- are merged by
+    one ``tta.merge``: no resized probability clip, stack or mean tensor is ever built."""
+    from torch.nn.functional import interpolate
+    from . import tta
+    scales = [float(s) for s in frame_scales]
+    entries = len(scales) * (2 if flip_lr else 1)
+    if not 1 <= entries <= tta.MAX_ENTRIES:
+        raise RuntimeError('expected 1 .. %d entries (scales, doubled by the flip), got %d' % (tta.MAX_ENTRIES, entries))
+    pair = bool(PAIR_FLIPS if pair_flips is None else pair_flips) and bool(flip_lr)
+    dev = next(net.parameters()).device
+    frames = video['frames'].to(dev, non_blocking=True).float().contiguous()
+    first = video['masks'][:1].to(dev, non_blocking=True).float()          # [1,K,H,W]: the only masks the network reads
+    N, _, H, W = frames.shape
+    n_objects = int(video['n_objects'])
+    sources, flipped = [], []
+    for fs in scales:
+        h, w = tta.scaled_size(H, W, fs)
+        clip = torch.empty(2 if pair else 1, N, 3, h, w, dtype=torch.float32, device=dev)
+        tta.resize_bilinear(frames, fs, out=clip[0])
+        mask = interpolate(first, scale_factor=fs, mode='nearest').int()
+        flow = flownet(clip[:1])
+        runs = [(clip[:1], mask, flow)]
+        if flip_lr:
+            mirrored = clip[1:] if pair else torch.empty_like(clip)
+            tta.resize_bilinear(frames, fs, flip=True, out=mirrored[0])
+            flow_m = torch.flip(flow, dims=[4])
+            flow_m[:, :, 0].neg_()
+            runs.append((mirrored, torch.flip(mask, dims=[3]), flow_m))
+        if pair:
+            runs = [(clip, torch.cat([runs[0][1], runs[1][1]]), torch.cat([runs[0][2], runs[1][2]]))]
+        for fr, mk, fl in runs:
+            B = fr.shape[0]
+            est = net(fr, mk.unsqueeze(1).expand(-1, N, -1, -1, -1), fl, torch.full((B, N), n_objects, dtype=torch.long), memorize_every,
+                      device=dev)
+            sources.extend(est[b] for b in range(B))
+        flipped.extend([False, True] if flip_lr else [False])
+    probs, labels = tta.merge([s.contiguous() for s in sources], flipped, (H, W))
+    return {'probs': probs, 'labels': labels}
+
+
+@torch.no_grad()
+def segment_video_u8(net, flownet, frames_u8, labels_u8, n_max_objects, mean, std, memorize_every=5, overlay=True,
+                     frame_scales=(1.0,), flip_lr=False):
     """One clip from what a folder of images holds to what the reference's driver writes (core/inference.py:50-71 with the test
     loader in front of it, utils/data_loaders.py:40-71), without leaving the device: ``frames_u8`` uint8 [N,H,W,3] RGB,
     ``labels_u8`` uint8 palette label maps [N,H,W] or the first frame's [H,W] (only frame 0 is read by the network; the object ids
     are reorganised over whatever is given, as ReorganizeObjectID does over the clip).  Returns {'labels': uint8 [N,H,W],
     'overlay': uint8 [N,H,W,3] or None, 'n_objects': int} with the tensors on the model's device.  ``n_objects`` =
-    min(ids in the label maps - 1, n_max_objects) (utils/data_loaders.py:64) costs the one host synchronisation of the call."""
+    min(ids in the label maps - 1, n_max_objects) (utils/data_loaders.py:64) costs the one host synchronisation of the call.
+    With other ``frame_scales`` than (1.0,) or with ``flip_lr`` the labels come from ``segment_video_tta`` (TEST.FRAME_SCALES and
+    TEST.FLIP_LR of the reference's configuration); with the defaults that path is not entered."""
     dev = next(net.parameters()).device
     frames_u8 = frames_u8.to(dev, non_blocking=True).contiguous()
     labels_u8 = labels_u8.to(dev, non_blocking=True)
@@ -61,6 +119,10 @@ def segment_video_u8(net, flownet, frames_u8, labels_u8, n_max_objects, mean, st
     n_objects = min(int(n_ids) - 1, int(n_max_objects))
     if n_objects < 0:
         raise RuntimeError('the label maps hold no id but the ignored one: there is nothing to segment')
+    if tuple(float(s) for s in frame_scales) != (1.0,) or flip_lr:
+        labels = segment_video_tta(net, flownet, {'frames': frames, 'masks': masks, 'n_objects': n_objects}, frame_scales, flip_lr,
+                                   memorize_every)['labels']
+        return {'labels': labels, 'overlay': clip_io.overlay(frames, labels, mean, std) if overlay else None, 'n_objects': n_objects}
     clip = frames.unsqueeze(0)
     flows = flownet(clip)
     est = net(clip, masks.unsqueeze(0), flows, torch.full((1, N), n_objects, dtype=torch.long), memorize_every, device=dev)

@@ -1408,3 +1408,74 @@ def overlay(frames, labels, mean, std, ignore_idx=255, alpha=0.4):
                                   float(alpha), int(ignore_idx), _ptr(out), _ptr(ws), ws.numel() * 4, _stream(dev))
     _lib.check(rc, 'rmnet_overlay_u8')
     return out
+
+
+# ------------------------------------------------------------------------------------------------ multi-scale inference (csrc/tta.hip)
+TTA_MAX_ENTRIES = 8            # RMNET_TTA_MAX_ENTRIES
+
+
+def resize_bilinear(x, out_h, out_w, scale_h, scale_w, flip=False, out=None):
+    """x float32 [..., Hs, Ws] on the GPU -> float32 [..., out_h, out_w]: torch's bilinear formula with align_corners=False in plain
+    fp32, every product and sum rounded on its own (include/rmnet_hip.h H1).  ``scale_h``, ``scale_w`` are the source steps per
+    output pixel, rounded to float32 here; F.interpolate(scale_factor=fs) uses float(1.0 / fs).  ``flip`` writes every row
+    mirrored.  ``out``: a contiguous float32 tensor of the result's shape to write into (a slice of a batch, say)."""
+    _check(x, 'x')
+    if x.dim() < 2:
+        raise RuntimeError('x must be [..., H, W]')
+    lib = _lib.load()
+    Hs, Ws = x.shape[-2:]
+    P = x.numel() // max(Hs * Ws, 1)
+    dev = x.device
+    shape = tuple(x.shape[:-2]) + (int(out_h), int(out_w))
+    with torch.cuda.device(dev):
+        if out is None:
+            out = torch.empty(shape, dtype=torch.float32, device=dev)
+        else:
+            _check(out, 'out')
+            if tuple(out.shape) != shape or out.device != dev:
+                raise RuntimeError('out must be %s on the device of x' % (shape,))
+        rc = lib.rmnet_resize_bilinear_f32(_ptr(x), P, Hs, Ws, int(out_h), int(out_w), float(scale_h), float(scale_w), int(bool(flip)),
+                                           _ptr(out), _stream(dev))
+    _lib.check(rc, 'rmnet_resize_bilinear_f32')
+    return out
+
+
+def tta_merge(sources, flipped, H, W, want_labels=True, mean=None, labels=None):
+    """sources: 1 .. 8 float32 [N,K,hs_e,ws_e] GPU tensors, flipped: one flag each -> (mean float32 [N,K,H,W], labels uint8 [N,H,W] or
+    None) in one launch: every source resized to (H, W) (F.interpolate(size=), a flipped source read mirrored), summed in entry order,
+    divided by the number of entries; the labels are the first index of the maximum of the means (include/rmnet_hip.h H1).  ``mean``
+    and ``labels`` may be given as contiguous buffers to write into; without ``want_labels`` a given label buffer is left alone."""
+    sources, flipped = list(sources), [int(bool(f)) for f in flipped]
+    E = len(sources)
+    if not 1 <= E <= TTA_MAX_ENTRIES or len(flipped) != E:
+        raise RuntimeError('expected 1 .. %d sources and one flag for each' % TTA_MAX_ENTRIES)
+    for s in sources:
+        _check(s, 'source')
+        if s.dim() != 4 or s.shape[:2] != sources[0].shape[:2] or s.device != sources[0].device:
+            raise RuntimeError('the sources must be [N, K, h, w] with the same N and K on one device')
+    lib = _lib.load()
+    N, K = sources[0].shape[:2]
+    H, W, dev = int(H), int(W), sources[0].device
+    with torch.cuda.device(dev):
+        if mean is None:
+            mean = torch.empty(N, K, H, W, dtype=torch.float32, device=dev)
+        else:
+            _check(mean, 'mean')
+            if tuple(mean.shape) != (N, K, H, W):
+                raise RuntimeError('mean must be [N, K, H, W]')
+        if want_labels:
+            if labels is None:
+                labels = torch.empty(N, H, W, dtype=torch.uint8, device=dev)
+            else:
+                _check(labels, 'labels', dtype=torch.uint8)
+                if tuple(labels.shape) != (N, H, W):
+                    raise RuntimeError('labels must be [N, H, W]')
+        ptrs = (ctypes.c_void_p * E)(*[s.data_ptr() for s in sources])
+        hs = (ctypes.c_int * E)(*[s.shape[2] for s in sources])
+        ws = (ctypes.c_int * E)(*[s.shape[3] for s in sources])
+        fl = (ctypes.c_int * E)(*flipped)
+        rc = lib.rmnet_tta_merge_f32(ctypes.cast(ptrs, ctypes.c_void_p), ctypes.cast(hs, ctypes.c_void_p), ctypes.cast(ws, ctypes.c_void_p),
+                                     ctypes.cast(fl, ctypes.c_void_p), E, N, K, H, W, _ptr(mean), _ptr(labels) if want_labels else None,
+                                     _stream(dev))
+    _lib.check(rc, 'rmnet_tta_merge_f32')
+    return mean, (labels if want_labels else None)
