@@ -626,6 +626,50 @@ int rmnet_resize_bilinear_f32(const float *src, int P, int Hs, int Ws, int Hd, i
 int rmnet_tta_merge_f32(const float *const *srcs, const int *hs, const int *ws, const int *flipped, int E, int N, int K, int H,
                         int W, float *mean, uint8_t *labels, void *stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * I1  Objects that are first annotated in the middle of a clip, the YouTube-VOS protocol (additive exports, same ABI version;
+ *     csrc/late_objects.hip).
+ * Replaces: the np.unique of every label map behind the loader's cumulative object count (utils/data_loaders.py:58-65) and
+ *           behind existing_objects (models/rmnet.py:398-407, 438), and the per-frame index writes of models/rmnet.py:436-448
+ *           with the F.softmax of :450, without one-hot masks of any frame but the first.
+ *
+ * rmnet_label_presence_u8: labels [N,H,W] uint8 at ANY byte alignment -> presence [N,8] uint32: bit (v & 31) of word (v >> 5) of
+ *     row n is set exactly when byte value v occurs in frame n.  The entry zeroes presence on the stream ahead of its one launch
+ *     (a memset node under graph capture), so the caller initialises nothing.  A frame is read as a head of up to 15 bytes in
+ *     front of the first 16-byte boundary, 16-byte loads, and a tail of up to 15 bytes; rmnet_label_presence_chunk_bytes() is
+ *     the number of body bytes one workgroup takes (pure host arithmetic).  The words are OR-ed together with integer atomics,
+ *     which commute: the same bits after every call.  No LDS, no workspace.
+ * RMNET_E_INVALID_ARG for a NULL pointer, N, H or W < 1 or a presence that is not 4-byte aligned; RMNET_E_UNSUPPORTED for
+ * N*H*W >= 2^31.
+ *
+ * rmnet_object_edit_softmax_f32: one frame of models/rmnet.py:436-450 in one pass.
+ *     logit  f32 [B,K,H,W], slice b at logit + b * logit_batch_stride (elements); EDITED IN PLACE
+ *     labels uint8 [B,H,W], slice b at labels + b * labels_batch_stride: frame t's raw label maps; NULL when no action is 2
+ *            (an action 2 without a label map injects m = 0 everywhere)
+ *     lut    uint8 [B,256]: ReorganizeObjectID's table of every clip (see rmnet_labels_onehot_u8)
+ *     action uint8 [B,K] on the device: 0 (and every value above 2) keeps the channel, 1 marks it absent, 2 injects
+ *     prob   f32 [B,K,H,W], slice b at prob + b * prob_batch_stride: fully written; with the stride it may be est[:, t] of a
+ *            [B,N,K,H,W] tensor.  Must not overlap logit.
+ *   absent  l = -16.1181f
+ *   inject  l = fl(fl(m * 32.0605f) - 16.1181f), m = (lut[b][label] == k) as 1.0f / 0.0f: fp32, one rounding per operation, as
+ *           torch evaluates masks.float() * 32.0605 - 16.1181
+ *   keep    the stored bits are neither touched nor rewritten
+ *   soft-max  mx = l_0, mx = fmaxf(mx, l_k) for k ascending;  sum = e_0, sum = fl(sum + e_k) for k ascending with
+ *           e_k = expf(fl(l_k - mx));  p_k = fl(e_k / sum), a true division.  expf is the device library's, the one
+ *           rmnet_soft_aggregate_f32 calls.
+ *     1 <= K <= 255.  NaN logits are out of scope: fmaxf passes over a NaN, so the pixel's other channels would be
+ *     normalised as if it were not there while its own probability is a NaN.
+ *     A lane owns 4 consecutive pixels when H*W, both strides and both float pointers allow 16-byte accesses, else one.
+ * RMNET_E_INVALID_ARG for a NULL pointer other than labels, B, H or W < 1, K outside 1 .. 255, a float pointer not aligned to
+ * 4 bytes or a batch stride smaller than the slice it steps over (K*H*W; H*W for labels); RMNET_E_UNSUPPORTED for B > 65535
+ * or an element index (a stride, K*H*W, or (B - 1) * stride + slice) of 2^31 or more.
+ * ------------------------------------------------------------------------------------------- */
+int rmnet_label_presence_chunk_bytes(void);
+int rmnet_label_presence_u8(const uint8_t *labels, int N, int H, int W, uint32_t *presence, void *stream);
+int rmnet_object_edit_softmax_f32(float *logit, long long logit_batch_stride, const uint8_t *labels, long long labels_batch_stride,
+                                  const uint8_t *lut, const uint8_t *action, float *prob, long long prob_batch_stride, int B, int K,
+                                  int H, int W, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

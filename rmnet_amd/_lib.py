@@ -144,6 +144,11 @@ SIGNATURES = {
     'rmnet_tta_merge_f32': (ctypes.c_int, [
         c_hostp, c_hostp, c_hostp, c_hostp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_f32p,
         ctypes.c_void_p, ctypes.c_void_p]),
+    'rmnet_label_presence_chunk_bytes': (ctypes.c_int, []),
+    'rmnet_label_presence_u8': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]),
+    'rmnet_object_edit_softmax_f32': (ctypes.c_int, [
+        c_f32p, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_void_p, c_f32p, ctypes.c_longlong,
+        ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
 }
 
 ABI_VERSION = 6

@@ -77,6 +77,16 @@ def onehot_labels(labels, K, lut=None):
     return (m.unsqueeze(1) == ids).to(torch.uint8)
 
 
+def restore_ids(labels, ids):
+    """labels [...] of plane indices (what ``argmax_labels`` returns) -> uint8 [...] in the clip's own ids: ``ids[labels]`` with
+    ``ids`` the ascending raw ids (``reorganize_lut``'s inverse; ``ObjectPlan.ids``).  A plane beyond the ids (no object of the
+    clip lives there) maps to 0, so no index leaves the table."""
+    ids = torch.as_tensor(ids, dtype=torch.uint8, device=labels.device).reshape(-1)
+    table = torch.zeros(256, dtype=torch.uint8, device=labels.device)
+    table[:ids.numel()] = ids
+    return table[labels.to(torch.uint8).to(torch.int64)]
+
+
 def argmax_labels(prob):
     """prob [N,K,H,W] -> uint8 [N,H,W], the first index of the maximum over K (1 <= K <= 255)."""
     if prob.dim() != 4 or not 1 <= prob.shape[1] <= 255:

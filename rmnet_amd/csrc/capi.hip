@@ -275,4 +275,17 @@ int rmnet_tta_merge_f32(const float* const* srcs, const int* hs, const int* ws, 
   return launch_tta_merge(srcs, hs, ws, flipped, E, N, K, H, W, mean, labels, static_cast<hipStream_t>(stream));
 }
 
+int rmnet_label_presence_chunk_bytes(void) { return label_presence_chunk(); }
+
+int rmnet_label_presence_u8(const uint8_t* labels, int N, int H, int W, uint32_t* presence, void* stream) {
+  return launch_label_presence(labels, N, H, W, presence, static_cast<hipStream_t>(stream));
+}
+
+int rmnet_object_edit_softmax_f32(float* logit, long long logit_batch_stride, const uint8_t* labels, long long labels_batch_stride,
+                                  const uint8_t* lut, const uint8_t* action, float* prob, long long prob_batch_stride, int B, int K, int H,
+                                  int W, void* stream) {
+  return launch_object_edit_softmax(logit, logit_batch_stride, labels, labels_batch_stride, lut, action, prob, prob_batch_stride, B, K, H,
+                                    W, static_cast<hipStream_t>(stream));
+}
+
 }  // extern "C"

@@ -422,6 +422,12 @@ int launch_resize_bilinear(const float* src, int P, int Hs, int Ws, int Hd, int 
 int launch_tta_merge(const float* const* srcs, const int* hs, const int* ws, const int* flipped, int E, int N, int K, int H, int W,
                      float* mean, uint8_t* labels, hipStream_t st);
 
+// late_objects.hip
+int label_presence_chunk();                       // bytes of a frame's body per workgroup (tests size their planes by it)
+int launch_label_presence(const uint8_t* labels, int N, int H, int W, uint32_t* presence, hipStream_t st);
+int launch_object_edit_softmax(float* logit, long long logit_bs, const uint8_t* labels, long long labels_bs, const uint8_t* lut,
+                               const uint8_t* action, float* prob, long long prob_bs, int B, int K, int H, int W, hipStream_t st);
+
 inline int check_launch() { return hipGetLastError() == hipSuccess ? RMNET_OK : RMNET_E_LAUNCH; }
 
 }  // namespace rmnet

@@ -95,7 +95,7 @@ def segment_video_tta(net, flownet, video, frame_scales=(1.0,), flip_lr=False, m
 
 @torch.no_grad()
 def segment_video_u8(net, flownet, frames_u8, labels_u8, n_max_objects, mean, std, memorize_every=5, overlay=True,
-                     frame_scales=(1.0,), flip_lr=False):
+                     frame_scales=(1.0,), flip_lr=False, new_objects=False):
     """One clip from what a folder of images holds to what the reference's driver writes (core/inference.py:50-71 with the test
     loader in front of it, utils/data_loaders.py:40-71), without leaving the device: ``frames_u8`` uint8 [N,H,W,3] RGB,
     ``labels_u8`` uint8 palette label maps [N,H,W] or the first frame's [H,W] (only frame 0 is read by the network; the object ids
@@ -103,7 +103,20 @@ def segment_video_u8(net, flownet, frames_u8, labels_u8, n_max_objects, mean, st
     'overlay': uint8 [N,H,W,3] or None, 'n_objects': int} with the tensors on the model's device.  ``n_objects`` =
     min(ids in the label maps - 1, n_max_objects) (utils/data_loaders.py:64) costs the one host synchronisation of the call.
     With other ``frame_scales`` than (1.0,) or with ``flip_lr`` the labels come from ``segment_video_tta`` (TEST.FRAME_SCALES and
-    TEST.FLIP_LR of the reference's configuration); with the defaults that path is not entered."""
+    TEST.FLIP_LR of the reference's configuration); with the defaults that path is not entered.
+
+    ``new_objects=True`` is the YouTube-VOS protocol: an object may first be annotated several frames into the clip.  ``labels_u8``
+    must then be [N,H,W] (frames without an annotation hold the ids of whatever is annotated there, e.g. all background: the
+    count is cumulative).  ``object_plan.label_presence`` and ``appearance_plan`` replace ``reorganize_lut``'s count -- their one
+    download is the call's host synchronisation --, only frame 0 is turned into one-hot masks, and the network injects every new
+    object at the frame where the clamped cumulative count changes and keeps it absent until then (models/rmnet.py:436-450).
+    The result also holds 'ids' (uint8, the clip's raw ids ascending: ``clip_io.restore_ids(labels, ids)`` gives the label maps in
+    the clip's own ids, as a submission wants them) and 'n_objects_per_frame' (list); 'n_objects' is the last frame's count.
+    It cannot be combined with other ``frame_scales`` than (1.0,) or with ``flip_lr`` (RuntimeError): a nearest-resized label map
+    can lose a small object and with it an injection, so every scale needs a plan of its own, which is left to a later change."""
+    if new_objects:
+        return _segment_video_u8_new_objects(net, flownet, frames_u8, labels_u8, n_max_objects, mean, std, memorize_every, overlay,
+                                             frame_scales, flip_lr)
     dev = next(net.parameters()).device
     frames_u8 = frames_u8.to(dev, non_blocking=True).contiguous()
     labels_u8 = labels_u8.to(dev, non_blocking=True)
@@ -128,6 +141,29 @@ def segment_video_u8(net, flownet, frames_u8, labels_u8, n_max_objects, mean, st
     est = net(clip, masks.unsqueeze(0), flows, torch.full((1, N), n_objects, dtype=torch.long), memorize_every, device=dev)
     labels = clip_io.argmax_labels(est[0].contiguous())
     return {'labels': labels, 'overlay': clip_io.overlay(frames, labels, mean, std) if overlay else None, 'n_objects': n_objects}
+
+
+def _segment_video_u8_new_objects(net, flownet, frames_u8, labels_u8, n_max_objects, mean, std, memorize_every, overlay, frame_scales,
+                                  flip_lr):
+    from . import object_plan
+    if tuple(float(s) for s in frame_scales) != (1.0,) or flip_lr:
+        raise RuntimeError('new_objects cannot be combined with frame_scales / flip_lr: every scale would need its own plan')
+    if labels_u8.dim() != 3 or labels_u8.shape[0] != frames_u8.shape[0]:
+        raise RuntimeError('new_objects needs the label maps of every frame, [N, H, W]')
+    dev = next(net.parameters()).device
+    frames_u8 = frames_u8.to(dev, non_blocking=True).contiguous()
+    labels_u8 = labels_u8.to(dev, non_blocking=True).contiguous()
+    frames = clip_io.normalize_frames(frames_u8, mean, std)
+    plan = object_plan.appearance_plan(object_plan.label_presence(labels_u8), n_max_objects)       # (the host synchronisation)
+    if plan.n_max < 0:
+        raise RuntimeError('the label maps hold no id but the ignored one: there is nothing to segment')
+    first = clip_io.onehot_labels(labels_u8[:1], plan.K, plan.lut)                                  # [1,K,H,W]
+    clip = frames.unsqueeze(0)
+    flows = flownet(clip)
+    est = net(clip, first.unsqueeze(0), flows, None, memorize_every, device=dev, object_plan=(labels_u8.unsqueeze(0), [plan]))
+    labels = clip_io.argmax_labels(est[0].contiguous())
+    return {'labels': labels, 'overlay': clip_io.overlay(frames, labels, mean, std) if overlay else None, 'n_objects': plan.n_max,
+            'ids': plan.ids_dev, 'n_objects_per_frame': list(plan.n_objects)}
 
 
 def write_segmentations(folder, images):

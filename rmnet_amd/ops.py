@@ -1479,3 +1479,70 @@ def tta_merge(sources, flipped, H, W, want_labels=True, mean=None, labels=None):
                                      _stream(dev))
     _lib.check(rc, 'rmnet_tta_merge_f32')
     return mean, (labels if want_labels else None)
+
+
+# ------------------------------------------------------------------------------------------------ late objects (csrc/late_objects.hip)
+def label_presence_chunk_bytes():
+    """Bytes of a frame's 16-byte-aligned body that one workgroup of the presence kernel reads (host arithmetic)."""
+    return int(_lib.load().rmnet_label_presence_chunk_bytes())
+
+
+def label_presence(labels):
+    """labels uint8 [N,H,W] on the GPU, contiguous, at any byte offset -> int32 [N,8]: the 256-bit set of the byte values of every
+    frame, bit ``v & 31`` of word ``v >> 5`` (the C entry's uint32 words, carried as int32: the same bits).  One memset node and
+    one launch on the current stream, no host synchronisation (include/rmnet_hip.h I1)."""
+    if not isinstance(labels, torch.Tensor) or labels.dim() != 3:
+        raise RuntimeError('labels must be a [N, H, W] tensor')
+    _check(labels, 'labels', dtype=torch.uint8)
+    lib = _lib.load()
+    N, H, W = labels.shape
+    dev = labels.device
+    with torch.cuda.device(dev):
+        out = torch.empty(max(N, 0), 8, dtype=torch.int32, device=dev)
+        rc = lib.rmnet_label_presence_u8(_ptr(labels), N, H, W, _ptr(out), _stream(dev))
+    _lib.check(rc, 'rmnet_label_presence_u8')
+    return out
+
+
+def _batch_slices(t, name, inner, dtype):
+    """``t`` must be [B, *inner] of ``dtype`` on the GPU with every batch slice contiguous; returns its batch stride in elements."""
+    if not isinstance(t, torch.Tensor) or t.dim() != len(inner) + 1 or tuple(t.shape[1:]) != tuple(inner):
+        raise RuntimeError('%s must be [B, %s]' % (name, ', '.join(str(i) for i in inner)))
+    if t.dtype != dtype:
+        raise RuntimeError('%s must be %s, got %s' % (name, dtype, t.dtype))
+    if not t.is_cuda:
+        raise RuntimeError('%s must be a CUDA tensor' % name)
+    if not t[0].is_contiguous():
+        raise RuntimeError('every batch slice of %s must be contiguous' % name)
+    return int(t.stride(0)) if t.shape[0] > 1 else int(t[0].numel())
+
+
+def object_edit_softmax(logit, labels, lut, action, prob):
+    """One frame of models/rmnet.py:436-450 in one launch: ``logit`` float32 [B,K,H,W] is edited in place per ``action`` uint8 [B,K]
+    (0 keep, 1 absent = -16.1181f, 2 inject fl(fl(m * 32.0605f) - 16.1181f) with m = (lut[b][label] == k)), then its soft-max
+    over K is written to ``prob`` float32 [B,K,H,W].  ``labels`` uint8 [B,H,W] are frame t's raw label maps (None when no action
+    is 2), ``lut`` uint8 [B,256] the clips' id tables.  logit, labels and prob may be batch-strided views whose slices are
+    contiguous (``est[:, t]``, ``labels[:, t]``); lut and action are contiguous.  1 <= K <= 255.  Returns ``prob``."""
+    if not isinstance(logit, torch.Tensor) or logit.dim() != 4:
+        raise RuntimeError('logit must be [B, K, H, W]')
+    B, K, H, W = logit.shape
+    if not 1 <= K <= 255:
+        raise RuntimeError('expected 1 <= K <= 255, got %d' % K)
+    if not isinstance(prob, torch.Tensor) or tuple(prob.shape) != (B, K, H, W):
+        raise RuntimeError('prob must be [B, K, H, W] like logit')
+    logit_bs = _batch_slices(logit, 'logit', (K, H, W), torch.float32)
+    prob_bs = _batch_slices(prob, 'prob', (K, H, W), torch.float32)
+    labels_bs = _batch_slices(labels, 'labels', (H, W), torch.uint8) if labels is not None else 0
+    _check(lut, 'lut', dtype=torch.uint8)
+    _check(action, 'action', dtype=torch.uint8)
+    if tuple(lut.shape) != (B, 256) or tuple(action.shape) != (B, K) or prob.shape[0] != B or (labels is not None and labels.shape[0] != B):
+        raise RuntimeError('expected lut [B, 256], action [B, K] and the same B everywhere')
+    dev = logit.device
+    if any(t is not None and t.device != dev for t in (labels, lut, action, prob)):
+        raise RuntimeError('every tensor must be on the device of logit')
+    lib = _lib.load()
+    with torch.cuda.device(dev):
+        rc = lib.rmnet_object_edit_softmax_f32(_ptr(logit), logit_bs, _ptr(labels), labels_bs, _ptr(lut), _ptr(action), _ptr(prob), prob_bs,
+                                               B, K, H, W, _stream(dev))
+    _lib.check(rc, 'rmnet_object_edit_softmax_f32')
+    return prob

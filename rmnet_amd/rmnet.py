@@ -392,7 +392,7 @@ class RMNet(nn.Module):
 
     @torch.no_grad()
     def forward(self, frames, masks, optical_flows, n_objects, memorize_every, device=None, _exact=False, graph=None,
-                return_logits=False, _precision=None):
+                return_logits=False, _precision=None, object_plan=None):
         """models/rmnet.py:385-452.  frames [B,N,3,H,W] f32, masks [B,N,K,H,W] (one-hot, any int or
         float dtype), optical_flows [B,N,2,H,W] f32, n_objects [B,N] int -> est_masks [B,N,K,H,W]
         f32 on the GPU (the reference returns them on the host unless several GPUs are visible).
@@ -406,11 +406,21 @@ class RMNet(nn.Module):
         increment and the rare logit edits of models/rmnet.py:436-448 happen outside it.  Default OFF: measured on MI355X
         (bench.py extras) the single 480p stream is bound by the batch-1 convolutions, not by launches -- replay gives
         170 vs 168 frames/s with the memory pinned and LOSES on a free-running 67-frame clip (157 vs 164: the capture and
-        the four input copies per frame cost more than the launch gaps they remove)."""
+        the four input copies per frame cost more than the launch gaps they remove).
+
+        ``object_plan=(labels, plans)``: the clip-level bookkeeping of objects that appear mid-clip comes from
+        ``rmnet_amd.object_plan`` instead of from the masks -- ``labels`` uint8 [B,N,H,W] raw label maps on the device, ``plans``
+        one ``ObjectPlan`` per clip.  ``masks`` then need hold frame 0 only ([B,1,K,H,W] is accepted), ``n_objects`` is not read
+        (the plans hold the counts), no torch.unique runs, and on a frame with edits one ``ops.object_edit_softmax`` call edits
+        the logits and writes ``est[:, t]``.  Without it nothing changes."""
         self._inference_only()
         dev = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
         frames = frames.to(dev, non_blocking=True)
         optical_flows = optical_flows.to(dev, non_blocking=True)
+        plans = None
+        if object_plan is not None:
+            labels_dev, plans = object_plan
+            masks = masks[:, :1]                # frame 0 is the only one read
         masks_dev = masks.to(dev, non_blocking=True)
         B, N, _, H, W = frames.shape
         K = masks.shape[2]
@@ -419,10 +429,21 @@ class RMNet(nn.Module):
         logits = torch.zeros(B, N, K, H, W, device=dev) if return_logits else None   # (frame 0 has none: models/rmnet.py:397)
 
         # ---- clip-level bookkeeping, hoisted out of the frame loop (the only host syncs)
-        n_obj_host = n_objects.cpu()
-        n_max = [int(n_obj_host[b].max()) for b in range(B)]
-        existing = [torch.unique(torch.argmax(masks_dev[b, 0], dim=0)).tolist() for b in range(B)]
-        fresh = {j for j in range(1, N) if bool((n_obj_host[:, j] != n_obj_host[:, j - 1]).any())}
+        if plans is not None:                   # (none here: the plans were made from one download of the presence words)
+            if len(plans) != B or tuple(labels_dev.shape) != (B, N, H, W) or labels_dev.dtype != torch.uint8 or labels_dev.device != dev \
+                    or any(p.K != K or len(p.n_objects) != N for p in plans):
+                raise RuntimeError('object_plan must be (uint8 labels [B, N, H, W] on the device, one plan of N frames and K planes per clip)')
+            n_max = [p.n_max for p in plans]
+            fresh = set().union(*[p.fresh for p in plans])
+            edited = set().union(*[p.edited for p in plans])
+            lut_dev = torch.stack([p.lut for p in plans])                          # [B,256]
+            action_dev = torch.stack([p.action for p in plans], dim=1)             # [N,B,K]: a frame's rows are contiguous
+            inject = {t for t in edited if any((p.action_host[t] == 2).any() for p in plans)}
+        else:
+            n_obj_host = n_objects.cpu()
+            n_max = [int(n_obj_host[b].max()) for b in range(B)]
+            existing = [torch.unique(torch.argmax(masks_dev[b, 0], dim=0)).tolist() for b in range(B)]
+            fresh = {j for j in range(1, N) if bool((n_obj_host[:, j] != n_obj_host[:, j - 1]).any())}
         commit = set(range(0, N, memorize_every)) | fresh
         ctx = self._ClipContext(self, B, K, H, W, n_max, dev)
         bank = self.new_bank(ctx, sum(1 for j in commit if j <= N - 2) + 1, exact=_exact, precision=_precision)
@@ -452,6 +473,15 @@ class RMNet(nn.Module):
             prob = None
             if isinstance(logit, tuple):
                 logit, prob = logit     # fused tail: soft-max already done (valid if the logits stay as they are)
+            if plans is not None:
+                if t in edited:     # models/rmnet.py:436-450 in one launch, written straight into est[:, t]
+                    logit = logit.contiguous()
+                    ops.object_edit_softmax(logit, labels_dev[:, t] if t in inject else None, lut_dev, action_dev[t], est[:, t])
+                else:
+                    est[:, t] = F.softmax(logit, dim=1) if prob is None else prob
+                if return_logits:
+                    logits[:, t] = logit
+                continue
             if t in fresh:      # models/rmnet.py:436-441
                 prob = None
                 for b in range(B):
@@ -475,7 +505,7 @@ class RMNet(nn.Module):
             prev = set_split_conv_(self, False)
             try:
                 out = self.forward(frames, masks, optical_flows, n_objects, memorize_every, device=dev, _exact=_exact, graph=graph,
-                                   return_logits=return_logits, _precision=_precision)
+                                   return_logits=return_logits, _precision=_precision, object_plan=object_plan)
             finally:
                 restore_split_conv_(prev)
             inner = self.last_clip['reread']
@@ -488,13 +518,13 @@ class RMNet(nn.Module):
                 warnings.warn('rmnet_amd: %d merge(s) of the bank read timed out on this device (scheduling problem?); '
                               'the clip is re-read with the exact-fp32 kernels' % timeouts)
             out = self.forward(frames, masks, optical_flows, n_objects, memorize_every, device=dev, _exact=True,
-                               return_logits=return_logits)
+                               return_logits=return_logits, object_plan=object_plan)
             self.last_clip['reread'] = 'exact: value outside the bank\'s fp16 window'
             return out
         if self.read_precision == 'auto' and self.last_clip['read_precision'] in ('f16', 'qx') and logit_max > AUTO_LOGIT_BOUND:
             # 'auto' on a clip whose soft-max turned out peaked: the fp16-operand read is not inside the bar there (see __init__)
             out = self.forward(frames, masks, optical_flows, n_objects, memorize_every, device=dev, graph=graph,
-                               return_logits=return_logits, _precision='split')
+                               return_logits=return_logits, _precision='split', object_plan=object_plan)
             self.last_clip['reread'] = 'split: largest logit %.1f > %.1f' % (logit_max, AUTO_LOGIT_BOUND)
             self._auto_peaked = True        # (sticky: this network's later one-object clips start in 'split')
             return out
