@@ -670,6 +670,46 @@ int rmnet_object_edit_softmax_f32(float *logit, long long logit_batch_stride, co
                                   const uint8_t *lut, const uint8_t *action, float *prob, long long prob_batch_stride, int B, int K,
                                   int H, int W, void *stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * I2  I1 for a clip that runs at another scale, possibly mirrored: late objects under multi-scale and flipped inference
+ *     (additive exports, same ABI version; csrc/late_objects.hip).
+ * Replaces: F.interpolate(masks, scale_factor=fs, mode='nearest') and torch.flip of the one-hot masks of EVERY frame in
+ *           multi_scale_inference (utils/helpers.py:44-78) as far as models/rmnet.py:398-407, 436-450 read them: the
+ *           torch.unique(torch.argmax(masks[t])) of frame 0 and of every frame with new objects, and the injected plane.
+ * The sampling rule of one axis, for output index d of an axis with `in` source elements:
+ *     src(d) = min((int)floorf((float)d * scale), in - 1)
+ * with scale = (float)(1.0 / fs) for F.interpolate(scale_factor=fs) and the output size floor(double(in) * fs): torch's legacy
+ * 'nearest' mode as a plain formula.  (torch's own kernels copy an axis whose output size equals its input size or its double
+ * even when fs is neither 1 nor 2; this rule does not.)  Nearest-resizing one-hot planes and taking their argmax equals applying
+ * the clip's table to the sampled label, so nothing but the full-size label maps is read and no resized map is written.
+ *
+ * rmnet_label_presence_nearest_u8: labels [N,Hs,Ws] uint8 at ANY byte alignment and S scales -> presence [S,N,8] uint32: bit
+ *     (v & 31) of word (v >> 5) of row (s, n) is set exactly when v occurs among labels[n][src_h(y)][src_w(x)] for y < hd[s],
+ *     x < wd[s].  hd, wd, scale_h, scale_w are HOST arrays of S entries, copied into the launch.  All scales are covered by one
+ *     launch behind the memset the entry issues itself (a memset node under graph capture); integer atomics, the same bits
+ *     after every call; no LDS, no workspace.  rmnet_label_presence_nearest_rows() is the number of output rows of one scale
+ *     that one workgroup takes (pure host arithmetic).
+ * RMNET_E_INVALID_ARG for a NULL pointer, N, Hs, Ws, hd[s] or wd[s] < 1, S outside 1 .. RMNET_TTA_MAX_ENTRIES, a scale that is
+ * not finite and positive or a presence that is not 4-byte aligned; RMNET_E_UNSUPPORTED for a side above 2^24 (the float index
+ * must be exact) or N*Hs*Ws >= 2^31.
+ *
+ * rmnet_object_edit_softmax_nearest_f32: rmnet_object_edit_softmax_f32 on a frame of H x W whose labels are read from a
+ *     full-size map: labels uint8 [B,Hs,Ws], slice b at labels + b * labels_batch_stride, and pixel (y, x) of slot b takes
+ *     labels[b][src_h(y)][src_w(xx)] with xx = W - 1 - x when bit b of flip_bits is set (the slot holds a mirrored clip), else
+ *     x.  labels_batch_stride may be 0: every slot reads the same map (a clip and its mirrored twin; the maps are only read).
+ *     Everything else -- constants, walks, rounding, lane forms, strides -- is rmnet_object_edit_softmax_f32's: on a
+ *     materialised resized (and mirrored) label map that entry returns the same bits in logit and in prob.
+ * The refusals of rmnet_object_edit_softmax_f32, with H*W of labels replaced by Hs*Ws, and: RMNET_E_INVALID_ARG for Hs or
+ * Ws < 1 or a scale that is not finite and positive; RMNET_E_UNSUPPORTED for B > 64 (one flip bit per slot) or a side above 2^24.
+ * ------------------------------------------------------------------------------------------- */
+int rmnet_label_presence_nearest_rows(void);
+int rmnet_label_presence_nearest_u8(const uint8_t *labels, int N, int Hs, int Ws, const int *hd, const int *wd,
+                                    const float *scale_h, const float *scale_w, int S, uint32_t *presence, void *stream);
+int rmnet_object_edit_softmax_nearest_f32(float *logit, long long logit_batch_stride, const uint8_t *labels,
+                                          long long labels_batch_stride, int Hs, int Ws, float scale_h, float scale_w,
+                                          unsigned long long flip_bits, const uint8_t *lut, const uint8_t *action, float *prob,
+                                          long long prob_batch_stride, int B, int K, int H, int W, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

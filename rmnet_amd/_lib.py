@@ -149,6 +149,14 @@ SIGNATURES = {
     'rmnet_object_edit_softmax_f32': (ctypes.c_int, [
         c_f32p, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_void_p, c_f32p, ctypes.c_longlong,
         ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
+    'rmnet_label_presence_nearest_rows': (ctypes.c_int, []),
+    'rmnet_label_presence_nearest_u8': (ctypes.c_int, [
+        ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_hostp, c_hostp, c_hostp, c_hostp, ctypes.c_int, ctypes.c_void_p,
+        ctypes.c_void_p]),
+    'rmnet_object_edit_softmax_nearest_f32': (ctypes.c_int, [
+        c_f32p, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_longlong, ctypes.c_int, ctypes.c_int, ctypes.c_float, ctypes.c_float,
+        ctypes.c_ulonglong, ctypes.c_void_p, ctypes.c_void_p, c_f32p, ctypes.c_longlong, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+        ctypes.c_int, ctypes.c_void_p]),
 }
 
 ABI_VERSION = 6

@@ -288,4 +288,19 @@ int rmnet_object_edit_softmax_f32(float* logit, long long logit_batch_stride, co
                                     W, static_cast<hipStream_t>(stream));
 }
 
+int rmnet_label_presence_nearest_rows(void) { return label_presence_nearest_rows(); }
+
+int rmnet_label_presence_nearest_u8(const uint8_t* labels, int N, int Hs, int Ws, const int* hd, const int* wd, const float* scale_h,
+                                    const float* scale_w, int S, uint32_t* presence, void* stream) {
+  return launch_label_presence_nearest(labels, N, Hs, Ws, hd, wd, scale_h, scale_w, S, presence, static_cast<hipStream_t>(stream));
+}
+
+int rmnet_object_edit_softmax_nearest_f32(float* logit, long long logit_batch_stride, const uint8_t* labels, long long labels_batch_stride,
+                                          int Hs, int Ws, float scale_h, float scale_w, unsigned long long flip_bits, const uint8_t* lut,
+                                          const uint8_t* action, float* prob, long long prob_batch_stride, int B, int K, int H, int W,
+                                          void* stream) {
+  return launch_object_edit_softmax_nearest(logit, logit_batch_stride, labels, labels_batch_stride, Hs, Ws, scale_h, scale_w, flip_bits, lut,
+                                            action, prob, prob_batch_stride, B, K, H, W, static_cast<hipStream_t>(stream));
+}
+
 }  // extern "C"

@@ -427,6 +427,12 @@ int label_presence_chunk();                       // bytes of a frame's body per
 int launch_label_presence(const uint8_t* labels, int N, int H, int W, uint32_t* presence, hipStream_t st);
 int launch_object_edit_softmax(float* logit, long long logit_bs, const uint8_t* labels, long long labels_bs, const uint8_t* lut,
                                const uint8_t* action, float* prob, long long prob_bs, int B, int K, int H, int W, hipStream_t st);
+int label_presence_nearest_rows();                // output rows of one scale per workgroup
+int launch_label_presence_nearest(const uint8_t* labels, int N, int Hs, int Ws, const int* hd, const int* wd, const float* scale_h,
+                                  const float* scale_w, int S, uint32_t* presence, hipStream_t st);
+int launch_object_edit_softmax_nearest(float* logit, long long logit_bs, const uint8_t* labels, long long labels_bs, int Hs, int Ws,
+                                       float scale_h, float scale_w, unsigned long long flip_bits, const uint8_t* lut, const uint8_t* action,
+                                       float* prob, long long prob_bs, int B, int K, int H, int W, hipStream_t st);
 
 inline int check_launch() { return hipGetLastError() == hipSuccess ? RMNET_OK : RMNET_E_LAUNCH; }
 

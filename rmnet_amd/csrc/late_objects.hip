@@ -7,6 +7,13 @@
 //                 fl(fl(m * 32.0605f) - 16.1181f) with m = (lut[label] == k); then the soft-max over the K channels, written through
 //                 a batch stride so that it lands in est[:, t]
 //
+// and the same two for a clip that runs at another scale, possibly mirrored (multi_scale_inference, utils/helpers.py:44-78;
+// include/rmnet_hip.h I2), with the nearest-neighbour rule  src(d) = min((int)floorf((float)d * scale), in - 1)  per axis:
+//
+//   lo_presence_nearest   labels [N,Hs,Ws] u8 + S scales -> presence [S,N,8] u32: the ids that the nearest-resized map of every scale
+//                         would hold, without writing a resized map
+//   lo_edit_nearest       lo_edit with the label read at the sampled (and, per batch slot, mirrored) position of a full-size map
+//
 // Presence: a frame's bytes are cut into a head of up to 15 bytes in front of the first 16-byte boundary, 16-byte vectors and a
 // tail of up to 15 bytes, so a label map at any address is read with dwordx4 loads in the body.  A lane keeps the 256-bit set in
 // four 64-bit registers picked by compares (a dynamically indexed array would go to scratch), skips a byte that repeats its
@@ -96,6 +103,60 @@ __global__ __launch_bounds__(kThreads) void lo_presence(const uint8_t* __restric
   }
 }
 
+// ------------------------------------------------------------------------------------------------ nearest-resized presence
+// The source index of output index d on an axis of `in` elements: torch's legacy 'nearest' rule with scale = (float)(1.0 / factor).
+// d and in are at most 2^24, so (float)d and (float)(in - 1) are exact; the minimum is taken before the conversion, so a product
+// beyond the int range is clamped like any other.  The result is in 0 .. in - 1 for every finite positive scale.
+__device__ inline int nearest_src(int d, int in, float scale) { return (int)fminf(floorf((float)d * scale), (float)(in - 1)); }
+
+constexpr int kNearestRows = 64;                           // output rows of one scale per workgroup
+constexpr int kWaveRows = kNearestRows / (kThreads / RMNET_WAVE);      // consecutive output rows per wave
+
+struct NearestScales {
+  int hd[RMNET_TTA_MAX_ENTRIES], wd[RMNET_TTA_MAX_ENTRIES];
+  float scale_h[RMNET_TTA_MAX_ENTRIES], scale_w[RMNET_TTA_MAX_ENTRIES];
+};
+
+// grid: x = ceil(max Hd / kNearestRows), y = min(N, 65535), z = S.  The sampled set of a scale is separable, the rows {src(y)} times
+// the columns {src(x)}: workgroup j takes the output rows [j * kNearestRows, ...) of its scale, wave w of it kWaveRows consecutive
+// ones of those, and a lane the output columns lane, lane + 64, ...; it keeps a column's source index over the walk down its rows.
+// An output row that reads the source row of its predecessor (upscales) is skipped.  Workgroups and waves past a scale's last row
+// and lanes past its last column add nothing, but no lane leaves before the reduction: the cross-lane steps read every lane.
+__global__ __launch_bounds__(kThreads) void lo_presence_nearest(const uint8_t* __restrict__ labels, uint32_t* __restrict__ presence, NearestScales q,
+                                                                int N, int Hs, int Ws) {
+  const int s = blockIdx.z;
+  const int hd = q.hd[s], wd = q.wd[s];
+  const float scale_h = q.scale_h[s], scale_w = q.scale_w[s];
+  const int lane = threadIdx.x & (RMNET_WAVE - 1), wave = threadIdx.x / RMNET_WAVE;
+  const int y0 = (int)blockIdx.x * kNearestRows + wave * kWaveRows;
+  const int y_end = min(y0 + kWaveRows, hd);
+  const long long plane = (long long)Hs * Ws;
+  for (int n = blockIdx.y; n < N; n += gridDim.y) {
+    const uint8_t* frame = labels + n * plane;
+    Set256 set = {0ull, 0ull, 0ull, 0ull};
+    for (int x = lane; x < wd; x += RMNET_WAVE) {
+      const uint8_t* col = frame + nearest_src(x, Ws, scale_w);
+      unsigned prev = 256u;                                // no byte
+      int prev_row = -1;
+      for (int y = y0; y < y_end; ++y) {
+        const int sy = nearest_src(y, Hs, scale_h);
+        if (sy == prev_row) continue;
+        prev_row = sy;
+        const unsigned v = col[(long long)sy * Ws];
+        if (v != prev) set_add(set, v);
+        prev = v;
+      }
+    }
+    const unsigned long long w[4] = {set.w0, set.w1, set.w2, set.w3};
+    uint32_t* row = presence + ((long long)s * N + n) * 8;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      const unsigned word = wave_or((unsigned)(w[i >> 1] >> (32 * (i & 1))));
+      if (lane == 0 && word != 0u) atomicOr(row + i, word);
+    }
+  }
+}
+
 // ------------------------------------------------------------------------------------------------ edit + soft-max
 template <int V> __device__ inline void load_f(const float* src, float (&v)[V]) {
   if constexpr (V == 4) {
@@ -125,27 +186,10 @@ template <int V> __device__ inline void store_f(float* dst, const float (&v)[V])
   else dst[0] = v[0];
 }
 
-// grid: x = ceil(H*W / (kThreads * V)), y = B.  A lane owns V consecutive pixels and walks the K channels three times: the edit and
-// the maximum, the exponentials (parked in prob) and their sum, the division.  The action row is wave-uniform.
+// The three walks of a lane over the K channels of its V consecutive pixels: the edit and the maximum, the exponentials (parked in
+// prob) and their sum, the division.  `r` holds lut[label] of the pixels (256: no label map); the action row is wave-uniform.
 template <int V>
-__global__ __launch_bounds__(kThreads) void lo_edit(float* __restrict__ logit, long long logit_bs, const uint8_t* __restrict__ labels,
-                                                    long long labels_bs, const uint8_t* __restrict__ lut, const uint8_t* __restrict__ action,
-                                                    float* __restrict__ prob, long long prob_bs, int K, long long HW) {
-  const long long p = ((long long)blockIdx.x * kThreads + threadIdx.x) * V;
-  if (p >= HW) return;
-  const int b = blockIdx.y;
-  const uint8_t* act = action + (long long)b * K;
-  float* lg = logit + b * logit_bs + p;
-  float* pr = prob + b * prob_bs + p;
-  int r[V];
-#pragma unroll
-  for (int i = 0; i < V; ++i) r[i] = 256;
-  if (labels) {
-    const uint8_t* lab = labels + b * labels_bs + p;
-    const uint8_t* table = lut + b * 256;
-#pragma unroll
-    for (int i = 0; i < V; ++i) r[i] = table[lab[i]];
-  }
+__device__ inline void edit_walks(float* lg, float* pr, const uint8_t* act, const int (&r)[V], int K, long long HW) {
   float mx[V] = {};
   for (int k = 0; k < K; ++k) {
     const int a = act[k];
@@ -175,7 +219,59 @@ __global__ __launch_bounds__(kThreads) void lo_edit(float* __restrict__ logit, l
   }
 }
 
+// grid: x = ceil(H*W / (kThreads * V)), y = B.  A lane owns V consecutive pixels and walks the K channels three times (edit_walks).
+template <int V>
+__global__ __launch_bounds__(kThreads) void lo_edit(float* __restrict__ logit, long long logit_bs, const uint8_t* __restrict__ labels,
+                                                    long long labels_bs, const uint8_t* __restrict__ lut, const uint8_t* __restrict__ action,
+                                                    float* __restrict__ prob, long long prob_bs, int K, long long HW) {
+  const long long p = ((long long)blockIdx.x * kThreads + threadIdx.x) * V;
+  if (p >= HW) return;
+  const int b = blockIdx.y;
+  int r[V];
+#pragma unroll
+  for (int i = 0; i < V; ++i) r[i] = 256;
+  if (labels) {
+    const uint8_t* lab = labels + b * labels_bs + p;
+    const uint8_t* table = lut + b * 256;
+#pragma unroll
+    for (int i = 0; i < V; ++i) r[i] = table[lab[i]];
+  }
+  edit_walks<V>(logit + b * logit_bs + p, prob + b * prob_bs + p, action + (long long)b * K, r, K, HW);
+}
+
+// The same grid and lanes on a frame of H x W whose labels are read from a full-size map [B,Hs,Ws]: pixel (y, x) of slot b takes
+// labels[b][src(y)][src(flipped ? W - 1 - x : x)].  The V pixels of a lane are consecutive in the flattened frame; they stay inside
+// one row when W % 4 == 0, and otherwise the step to the next pixel wraps into the next row, so (y, x) is formed per pixel.
+template <int V>
+__global__ __launch_bounds__(kThreads) void lo_edit_nearest(float* __restrict__ logit, long long logit_bs, const uint8_t* __restrict__ labels,
+                                                            long long labels_bs, int Hs, int Ws, float scale_h, float scale_w,
+                                                            unsigned long long flip_bits, const uint8_t* __restrict__ lut,
+                                                            const uint8_t* __restrict__ action, float* __restrict__ prob, long long prob_bs, int K,
+                                                            int W, long long HW) {
+  const long long p = ((long long)blockIdx.x * kThreads + threadIdx.x) * V;
+  if (p >= HW) return;
+  const int b = blockIdx.y;
+  int r[V];
+#pragma unroll
+  for (int i = 0; i < V; ++i) r[i] = 256;
+  if (labels) {
+    const uint8_t* lab = labels + b * labels_bs;
+    const uint8_t* table = lut + b * 256;
+    const bool flipped = (flip_bits >> b) & 1ull;
+    int y = (int)(p / W), x = (int)(p - (long long)y * W);
+#pragma unroll
+    for (int i = 0; i < V; ++i) {
+      const int xx = flipped ? W - 1 - x : x;
+      r[i] = table[lab[(long long)nearest_src(y, Hs, scale_h) * Ws + nearest_src(xx, Ws, scale_w)]];
+      if (++x == W) { x = 0; ++y; }
+    }
+  }
+  edit_walks<V>(logit + b * logit_bs + p, prob + b * prob_bs + p, action + (long long)b * K, r, K, HW);
+}
+
 inline bool aligned(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
+inline bool good_scale(float s) { return s > 0.0f && s <= 3.0e38f; }        // finite and positive (false for a NaN)
+constexpr int kMaxSide = 1 << 24;                          // every index of a side is exact as a float
 
 }  // namespace
 
@@ -207,6 +303,54 @@ int launch_object_edit_softmax(float* logit, long long logit_bs, const uint8_t* 
   const dim3 grid((unsigned)((HW + per_block - 1) / per_block), (unsigned)B);
   if (vec) hipLaunchKernelGGL(lo_edit<4>, grid, dim3(kThreads), 0, st, logit, logit_bs, labels, labels_bs, lut, action, prob, prob_bs, K, HW);
   else hipLaunchKernelGGL(lo_edit<1>, grid, dim3(kThreads), 0, st, logit, logit_bs, labels, labels_bs, lut, action, prob, prob_bs, K, HW);
+  return check_launch();
+}
+
+int label_presence_nearest_rows() { return kNearestRows; }
+
+int launch_label_presence_nearest(const uint8_t* labels, int N, int Hs, int Ws, const int* hd, const int* wd, const float* scale_h,
+                                  const float* scale_w, int S, uint32_t* presence, hipStream_t st) {
+  if (!labels || !presence || !hd || !wd || !scale_h || !scale_w || N < 1 || Hs < 1 || Ws < 1 || !aligned(presence, 4))
+    return RMNET_E_INVALID_ARG;
+  if (S < 1 || S > RMNET_TTA_MAX_ENTRIES) return RMNET_E_INVALID_ARG;
+  NearestScales q = {};
+  int h_max = 0;
+  for (int s = 0; s < S; ++s) {
+    if (hd[s] < 1 || wd[s] < 1 || !good_scale(scale_h[s]) || !good_scale(scale_w[s])) return RMNET_E_INVALID_ARG;
+    q.hd[s] = hd[s]; q.wd[s] = wd[s]; q.scale_h[s] = scale_h[s]; q.scale_w[s] = scale_w[s];
+    h_max = hd[s] > h_max ? hd[s] : h_max;
+  }
+  if (Hs > kMaxSide || Ws > kMaxSide) return RMNET_E_UNSUPPORTED;
+  for (int s = 0; s < S; ++s)
+    if (hd[s] > kMaxSide || wd[s] > kMaxSide) return RMNET_E_UNSUPPORTED;
+  if ((long long)Hs * Ws * N >= (1LL << 31)) return RMNET_E_UNSUPPORTED;
+  if (hipMemsetAsync(presence, 0, (size_t)S * N * 8 * sizeof(uint32_t), st) != hipSuccess) return RMNET_E_LAUNCH;
+  const dim3 grid((unsigned)((h_max + kNearestRows - 1) / kNearestRows), (unsigned)(N < 65535 ? N : 65535), (unsigned)S);
+  hipLaunchKernelGGL(lo_presence_nearest, grid, dim3(kThreads), 0, st, labels, presence, q, N, Hs, Ws);
+  return check_launch();
+}
+
+int launch_object_edit_softmax_nearest(float* logit, long long logit_bs, const uint8_t* labels, long long labels_bs, int Hs, int Ws,
+                                       float scale_h, float scale_w, unsigned long long flip_bits, const uint8_t* lut, const uint8_t* action,
+                                       float* prob, long long prob_bs, int B, int K, int H, int W, hipStream_t st) {
+  if (!logit || !lut || !action || !prob || B < 1 || H < 1 || W < 1 || Hs < 1 || Ws < 1 || K < 1 || K > 255) return RMNET_E_INVALID_ARG;
+  if (!aligned(logit, 4) || !aligned(prob, 4) || !good_scale(scale_h) || !good_scale(scale_w)) return RMNET_E_INVALID_ARG;
+  const long long HW = (long long)H * W, HWs = (long long)Hs * Ws;
+  if (logit_bs < K * HW || prob_bs < K * HW || (labels && labels_bs != 0 && labels_bs < HWs)) return RMNET_E_INVALID_ARG;      // (0: one map for every slot)
+  const long long lim = 1LL << 31;
+  if (B > 64 || H > kMaxSide || W > kMaxSide || Hs > kMaxSide || Ws > kMaxSide) return RMNET_E_UNSUPPORTED;      // (one flip bit per slot)
+  if (K * HW >= lim || logit_bs >= lim || prob_bs >= lim || labels_bs >= lim || HWs >= lim) return RMNET_E_UNSUPPORTED;
+  if ((B - 1) * logit_bs + K * HW >= lim || (B - 1) * prob_bs + K * HW >= lim || (labels && (B - 1) * labels_bs + HWs >= lim))
+    return RMNET_E_UNSUPPORTED;
+  const bool vec = HW % 4 == 0 && aligned(logit, 16) && aligned(prob, 16) && logit_bs % 4 == 0 && prob_bs % 4 == 0;
+  const long long per_block = (long long)kThreads * (vec ? 4 : 1);
+  const dim3 grid((unsigned)((HW + per_block - 1) / per_block), (unsigned)B);
+  if (vec)
+    hipLaunchKernelGGL(lo_edit_nearest<4>, grid, dim3(kThreads), 0, st, logit, logit_bs, labels, labels_bs, Hs, Ws, scale_h, scale_w, flip_bits,
+                       lut, action, prob, prob_bs, K, W, HW);
+  else
+    hipLaunchKernelGGL(lo_edit_nearest<1>, grid, dim3(kThreads), 0, st, logit, logit_bs, labels, labels_bs, Hs, Ws, scale_h, scale_w, flip_bits,
+                       lut, action, prob, prob_bs, K, W, HW);
   return check_launch();
 }
 

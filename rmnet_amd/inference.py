@@ -45,7 +45,8 @@ PAIR_FLIPS = True
 
 
 @torch.no_grad()
-def segment_video_tta(net, flownet, video, frame_scales=(1.0,), flip_lr=False, memorize_every=5, pair_flips=None):
+def segment_video_tta(net, flownet, video, frame_scales=(1.0,), flip_lr=False, memorize_every=5, pair_flips=None, new_objects=False,
+                      n_max_objects=None):
     """One clip at several scales, optionally also mirrored left-right, merged on the device: multi_scale_inference
     (utils/helpers.py:44-78) followed by the driver's argmax.  ``video`` as for ``segment_video``.  Returns {'probs': float32
     [N,K,H,W], 'labels': uint8 [N,H,W]} on the model's device.
@@ -54,9 +55,19 @@ def segment_video_tta(net, flownet, video, frame_scales=(1.0,), flip_lr=False, m
     on the unflipped frames, and the flipped twin takes the mirrored flow with its x channel negated, as the reference does.  With
     ``pair_flips`` the two clips of a scale go through ONE ``net`` call as a batch of two (slot 1 holds the mirrored frames, written
     by the resize itself); otherwise through two calls.  The entries -- per scale the unflipped, then the flipped one -- are merged by
-    one ``tta.merge``: no resized probability clip, stack or mean tensor is ever built."""
+    one ``tta.merge``: no resized probability clip, stack or mean tensor is ever built.
+
+    ``new_objects=True`` is the YouTube-VOS protocol under the scales and the flip: ``video`` = {'frames', 'labels' uint8 [N,H,W] at
+    full size} and ``n_max_objects`` is the configuration's cap.  The reference resizes the one-hot masks of every frame by nearest
+    neighbour and counts the objects at full size; here one ``object_plan.label_presence``, one ``label_presence_scaled`` over all
+    scales and one ``appearance_plans`` -- the call's one host synchronisation for its bookkeeping -- give a plan per scale, which
+    serves the unflipped and the flipped pass alike.  Per scale the first frame's masks are the one-hot planes of frame 0 indexed
+    by ``tta.nearest_index`` (the plain formula, the rule the plans and the edits follow), and the network reads the full-size label
+    maps at the sampled, mirrored position where it injects an object.  The result also holds 'ids' and 'n_objects_per_frame'."""
     from torch.nn.functional import interpolate
     from . import tta
+    if new_objects:
+        return _segment_video_tta_new_objects(net, flownet, video, frame_scales, flip_lr, memorize_every, pair_flips, n_max_objects)
     scales = [float(s) for s in frame_scales]
     entries = len(scales) * (2 if flip_lr else 1)
     if not 1 <= entries <= tta.MAX_ENTRIES:
@@ -93,9 +104,59 @@ def segment_video_tta(net, flownet, video, frame_scales=(1.0,), flip_lr=False, m
     return {'probs': probs, 'labels': labels}
 
 
+def _segment_video_tta_new_objects(net, flownet, video, frame_scales, flip_lr, memorize_every, pair_flips, n_max_objects):
+    from . import object_plan, tta
+    if 'labels' not in video:
+        raise RuntimeError('new_objects needs video[\'labels\']: the uint8 label maps of every frame, [N, H, W]')
+    if n_max_objects is None:
+        raise RuntimeError('new_objects needs n_max_objects, the cap on the number of objects')
+    scales = [float(s) for s in frame_scales]
+    entries = len(scales) * (2 if flip_lr else 1)
+    if not 1 <= entries <= tta.MAX_ENTRIES:
+        raise RuntimeError('expected 1 .. %d entries (scales, doubled by the flip), got %d' % (tta.MAX_ENTRIES, entries))
+    pair = bool(PAIR_FLIPS if pair_flips is None else pair_flips) and bool(flip_lr)
+    dev = next(net.parameters()).device
+    frames = video['frames'].to(dev, non_blocking=True).float().contiguous()
+    labels = video['labels'].to(dev, non_blocking=True).contiguous()
+    N, _, H, W = frames.shape
+    if labels.dtype != torch.uint8 or tuple(labels.shape) != (N, H, W):
+        raise RuntimeError('new_objects needs the label maps of every frame, uint8 [N, H, W]')
+    plans = object_plan.appearance_plans(object_plan.label_presence(labels), object_plan.label_presence_scaled(labels, H, W, scales),
+                                         n_max_objects)                                             # (the host synchronisation)
+    if plans[0].n_max < 0:
+        raise RuntimeError('the label maps hold no id but the ignored one: there is nothing to segment')
+    first = clip_io.onehot_labels(labels[:1], plans[0].K, plans[0].lut)                             # [1,K,H,W], full size
+    sources, flipped = [], []
+    for fs, plan in zip(scales, plans):
+        h, w = tta.scaled_size(H, W, fs)
+        clip = torch.empty(2 if pair else 1, N, 3, h, w, dtype=torch.float32, device=dev)
+        tta.resize_bilinear(frames, fs, out=clip[0])
+        iy = torch.from_numpy(tta.nearest_index(h, H, fs)).to(dev)
+        ix = torch.from_numpy(tta.nearest_index(w, W, fs)).to(dev)
+        mask = first.index_select(2, iy).index_select(3, ix)                                        # [1,K,h,w]
+        flow = flownet(clip[:1])
+        runs = [(clip[:1], mask, flow, (False,))]
+        if flip_lr:
+            mirrored = clip[1:] if pair else torch.empty_like(clip)
+            tta.resize_bilinear(frames, fs, flip=True, out=mirrored[0])
+            flow_m = torch.flip(flow, dims=[4])
+            flow_m[:, :, 0].neg_()
+            runs.append((mirrored, torch.flip(mask, dims=[3]), flow_m, (True,)))
+        if pair:
+            runs = [(clip, torch.cat([runs[0][1], runs[1][1]]), torch.cat([runs[0][2], runs[1][2]]), (False, True))]
+        for fr, mk, fl, flips in runs:
+            B = fr.shape[0]
+            est = net(fr, mk.unsqueeze(1), fl, None, memorize_every, device=dev,
+                      object_plan=(labels.unsqueeze(0).expand(B, -1, -1, -1), [plan] * B, (fs, flips)))
+            sources.extend(est[b] for b in range(B))
+        flipped.extend([False, True] if flip_lr else [False])
+    probs, out = tta.merge([s.contiguous() for s in sources], flipped, (H, W))
+    return {'probs': probs, 'labels': out, 'ids': plans[0].ids_dev, 'n_objects_per_frame': list(plans[0].n_objects)}
+
+
 @torch.no_grad()
 def segment_video_u8(net, flownet, frames_u8, labels_u8, n_max_objects, mean, std, memorize_every=5, overlay=True,
-                     frame_scales=(1.0,), flip_lr=False, new_objects=False):
+                     frame_scales=(1.0,), flip_lr=False, new_objects=False, scale_plans=False):
     """One clip from what a folder of images holds to what the reference's driver writes (core/inference.py:50-71 with the test
     loader in front of it, utils/data_loaders.py:40-71), without leaving the device: ``frames_u8`` uint8 [N,H,W,3] RGB,
     ``labels_u8`` uint8 palette label maps [N,H,W] or the first frame's [H,W] (only frame 0 is read by the network; the object ids
@@ -112,11 +173,14 @@ def segment_video_u8(net, flownet, frames_u8, labels_u8, n_max_objects, mean, st
     object at the frame where the clamped cumulative count changes and keeps it absent until then (models/rmnet.py:436-450).
     The result also holds 'ids' (uint8, the clip's raw ids ascending: ``clip_io.restore_ids(labels, ids)`` gives the label maps in
     the clip's own ids, as a submission wants them) and 'n_objects_per_frame' (list); 'n_objects' is the last frame's count.
-    It cannot be combined with other ``frame_scales`` than (1.0,) or with ``flip_lr`` (RuntimeError): a nearest-resized label map
-    can lose a small object and with it an injection, so every scale needs a plan of its own, which is left to a later change."""
+    A nearest-resized label map can lose a small object and with it an injection, so under other ``frame_scales`` than (1.0,) or
+    ``flip_lr`` every scale needs a plan of its own: ``scale_plans=True`` makes them (``segment_video_tta(new_objects=True)``, one
+    host synchronisation as before) and mirrors what the reference's multi_scale_inference does with the masks of every frame.
+    ``scale_plans`` defaults to False, and the combination is then refused with a RuntimeError, as it was before the plans per
+    scale existed."""
     if new_objects:
         return _segment_video_u8_new_objects(net, flownet, frames_u8, labels_u8, n_max_objects, mean, std, memorize_every, overlay,
-                                             frame_scales, flip_lr)
+                                             frame_scales, flip_lr, scale_plans)
     dev = next(net.parameters()).device
     frames_u8 = frames_u8.to(dev, non_blocking=True).contiguous()
     labels_u8 = labels_u8.to(dev, non_blocking=True)
@@ -144,9 +208,10 @@ def segment_video_u8(net, flownet, frames_u8, labels_u8, n_max_objects, mean, st
 
 
 def _segment_video_u8_new_objects(net, flownet, frames_u8, labels_u8, n_max_objects, mean, std, memorize_every, overlay, frame_scales,
-                                  flip_lr):
+                                  flip_lr, scale_plans=False):
     from . import object_plan
-    if tuple(float(s) for s in frame_scales) != (1.0,) or flip_lr:
+    scaled = tuple(float(s) for s in frame_scales) != (1.0,) or bool(flip_lr)
+    if scaled and not scale_plans:
         raise RuntimeError('new_objects cannot be combined with frame_scales / flip_lr: every scale would need its own plan')
     if labels_u8.dim() != 3 or labels_u8.shape[0] != frames_u8.shape[0]:
         raise RuntimeError('new_objects needs the label maps of every frame, [N, H, W]')
@@ -154,6 +219,11 @@ def _segment_video_u8_new_objects(net, flownet, frames_u8, labels_u8, n_max_obje
     frames_u8 = frames_u8.to(dev, non_blocking=True).contiguous()
     labels_u8 = labels_u8.to(dev, non_blocking=True).contiguous()
     frames = clip_io.normalize_frames(frames_u8, mean, std)
+    if scaled:
+        r = segment_video_tta(net, flownet, {'frames': frames, 'labels': labels_u8}, frame_scales, flip_lr, memorize_every, new_objects=True,
+                              n_max_objects=n_max_objects)
+        return {'labels': r['labels'], 'overlay': clip_io.overlay(frames, r['labels'], mean, std) if overlay else None,
+                'n_objects': r['n_objects_per_frame'][-1], 'ids': r['ids'], 'n_objects_per_frame': r['n_objects_per_frame']}
     plan = object_plan.appearance_plan(object_plan.label_presence(labels_u8), n_max_objects)       # (the host synchronisation)
     if plan.n_max < 0:
         raise RuntimeError('the label maps hold no id but the ignored one: there is nothing to segment')

@@ -1517,12 +1517,47 @@ def _batch_slices(t, name, inner, dtype):
     return int(t.stride(0)) if t.shape[0] > 1 else int(t[0].numel())
 
 
-def object_edit_softmax(logit, labels, lut, action, prob):
+def label_presence_nearest_rows():
+    """Output rows of one scale that one workgroup of the nearest-resized presence kernel takes (host arithmetic)."""
+    return int(_lib.load().rmnet_label_presence_nearest_rows())
+
+
+def label_presence_nearest(labels, sizes, scales):
+    """labels uint8 [N,Hs,Ws] on the GPU, contiguous, at any byte offset; ``sizes``: 1 .. 8 pairs (hd, wd), ``scales``: as many
+    pairs (scale_h, scale_w) of source steps per output pixel -> int32 [S,N,8]: row (s, n) is the 256-bit set of the values among
+    labels[n][src(y)][src(x)], y < hd, x < wd, with src(d) = min(int(floorf(float(d) * scale)), in - 1): the ids the nearest-resized
+    label map of every scale would hold, without the map.  One memset node and one launch for all scales on the current stream, no
+    host synchronisation (include/rmnet_hip.h I2)."""
+    if not isinstance(labels, torch.Tensor) or labels.dim() != 3:
+        raise RuntimeError('labels must be a [N, H, W] tensor')
+    _check(labels, 'labels', dtype=torch.uint8)
+    sizes, scales = [(int(h), int(w)) for h, w in sizes], [(float(a), float(b)) for a, b in scales]
+    S = len(sizes)
+    if not 1 <= S <= TTA_MAX_ENTRIES or len(scales) != S:
+        raise RuntimeError('expected 1 .. %d sizes and one pair of scales for each' % TTA_MAX_ENTRIES)
+    lib = _lib.load()
+    N, Hs, Ws = labels.shape
+    dev = labels.device
+    hd, wd = (ctypes.c_int * S)(*[h for h, _ in sizes]), (ctypes.c_int * S)(*[w for _, w in sizes])
+    sh, sw = (ctypes.c_float * S)(*[a for a, _ in scales]), (ctypes.c_float * S)(*[b for _, b in scales])
+    with torch.cuda.device(dev):
+        out = torch.empty(S, max(N, 0), 8, dtype=torch.int32, device=dev)
+        rc = lib.rmnet_label_presence_nearest_u8(_ptr(labels), N, Hs, Ws, ctypes.cast(hd, ctypes.c_void_p), ctypes.cast(wd, ctypes.c_void_p),
+                                                 ctypes.cast(sh, ctypes.c_void_p), ctypes.cast(sw, ctypes.c_void_p), S, _ptr(out), _stream(dev))
+    _lib.check(rc, 'rmnet_label_presence_nearest_u8')
+    return out
+
+
+def object_edit_softmax(logit, labels, lut, action, prob, sampling=None):
     """One frame of models/rmnet.py:436-450 in one launch: ``logit`` float32 [B,K,H,W] is edited in place per ``action`` uint8 [B,K]
     (0 keep, 1 absent = -16.1181f, 2 inject fl(fl(m * 32.0605f) - 16.1181f) with m = (lut[b][label] == k)), then its soft-max
     over K is written to ``prob`` float32 [B,K,H,W].  ``labels`` uint8 [B,H,W] are frame t's raw label maps (None when no action
     is 2), ``lut`` uint8 [B,256] the clips' id tables.  logit, labels and prob may be batch-strided views whose slices are
-    contiguous (``est[:, t]``, ``labels[:, t]``); lut and action are contiguous.  1 <= K <= 255.  Returns ``prob``."""
+    contiguous (``est[:, t]``, ``labels[:, t]``); lut and action are contiguous.  1 <= K <= 255.  Returns ``prob``.
+
+    ``sampling = (scale_h, scale_w, flips)``: the frame is a resized clip's and ``labels`` are full-size maps uint8 [B,Hs,Ws] of any
+    size; pixel (y, x) of slot b reads labels[b][src(y)][src(W - 1 - x if flips[b] else x)] with the nearest rule of
+    ``label_presence_nearest`` (include/rmnet_hip.h I2).  ``flips``: one flag per slot, B <= 64."""
     if not isinstance(logit, torch.Tensor) or logit.dim() != 4:
         raise RuntimeError('logit must be [B, K, H, W]')
     B, K, H, W = logit.shape
@@ -1532,7 +1567,16 @@ def object_edit_softmax(logit, labels, lut, action, prob):
         raise RuntimeError('prob must be [B, K, H, W] like logit')
     logit_bs = _batch_slices(logit, 'logit', (K, H, W), torch.float32)
     prob_bs = _batch_slices(prob, 'prob', (K, H, W), torch.float32)
-    labels_bs = _batch_slices(labels, 'labels', (H, W), torch.uint8) if labels is not None else 0
+    Hs, Ws = H, W
+    if sampling is not None:
+        scale_h, scale_w, flips = float(sampling[0]), float(sampling[1]), [bool(f) for f in sampling[2]]
+        if len(flips) != B or B > 64:
+            raise RuntimeError('sampling needs one flip flag per batch slot and B <= 64')
+        if labels is not None:
+            if not isinstance(labels, torch.Tensor) or labels.dim() != 3:
+                raise RuntimeError('labels must be [B, Hs, Ws]')
+            Hs, Ws = labels.shape[1:]
+    labels_bs = _batch_slices(labels, 'labels', (Hs, Ws), torch.uint8) if labels is not None else 0
     _check(lut, 'lut', dtype=torch.uint8)
     _check(action, 'action', dtype=torch.uint8)
     if tuple(lut.shape) != (B, 256) or tuple(action.shape) != (B, K) or prob.shape[0] != B or (labels is not None and labels.shape[0] != B):
@@ -1542,7 +1586,14 @@ def object_edit_softmax(logit, labels, lut, action, prob):
         raise RuntimeError('every tensor must be on the device of logit')
     lib = _lib.load()
     with torch.cuda.device(dev):
-        rc = lib.rmnet_object_edit_softmax_f32(_ptr(logit), logit_bs, _ptr(labels), labels_bs, _ptr(lut), _ptr(action), _ptr(prob), prob_bs,
-                                               B, K, H, W, _stream(dev))
-    _lib.check(rc, 'rmnet_object_edit_softmax_f32')
+        if sampling is None:
+            rc = lib.rmnet_object_edit_softmax_f32(_ptr(logit), logit_bs, _ptr(labels), labels_bs, _ptr(lut), _ptr(action), _ptr(prob), prob_bs,
+                                                   B, K, H, W, _stream(dev))
+            what = 'rmnet_object_edit_softmax_f32'
+        else:
+            bits = sum(1 << b for b, f in enumerate(flips) if f)
+            rc = lib.rmnet_object_edit_softmax_nearest_f32(_ptr(logit), logit_bs, _ptr(labels), labels_bs, int(Hs), int(Ws), scale_h, scale_w, bits,
+                                                           _ptr(lut), _ptr(action), _ptr(prob), prob_bs, B, K, H, W, _stream(dev))
+            what = 'rmnet_object_edit_softmax_nearest_f32'
+    _lib.check(rc, what)
     return prob

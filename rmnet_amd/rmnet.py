@@ -412,14 +412,23 @@ class RMNet(nn.Module):
         ``rmnet_amd.object_plan`` instead of from the masks -- ``labels`` uint8 [B,N,H,W] raw label maps on the device, ``plans``
         one ``ObjectPlan`` per clip.  ``masks`` then need hold frame 0 only ([B,1,K,H,W] is accepted), ``n_objects`` is not read
         (the plans hold the counts), no torch.unique runs, and on a frame with edits one ``ops.object_edit_softmax`` call edits
-        the logits and writes ``est[:, t]``.  Without it nothing changes."""
+        the logits and writes ``est[:, t]``.  Without it nothing changes.
+
+        ``object_plan=(labels, plans, sampling)`` with ``sampling = (fs, flips)``: the clip runs at scale ``fs`` and batch slot b is
+        mirrored left-right when ``flips[b]`` (multi_scale_inference, utils/helpers.py:44-78).  ``labels`` are then the FULL-SIZE maps
+        uint8 [B,N,Hs,Ws], ``frames`` are at ``tta.scaled_size(Hs, Ws, fs)``, the plans are that scale's (``object_plan.
+        appearance_plans``; a mirrored slot takes the plan of its unmirrored twin) and the edits read the label at the sampled,
+        mirrored position (include/rmnet_hip.h I2).  Nothing else differs."""
         self._inference_only()
         dev = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
         frames = frames.to(dev, non_blocking=True)
         optical_flows = optical_flows.to(dev, non_blocking=True)
-        plans = None
+        plans, sampling = None, None
         if object_plan is not None:
-            labels_dev, plans = object_plan
+            if len(object_plan) == 3:
+                labels_dev, plans, sampling = object_plan
+            else:
+                labels_dev, plans = object_plan
             masks = masks[:, :1]                # frame 0 is the only one read
         masks_dev = masks.to(dev, non_blocking=True)
         B, N, _, H, W = frames.shape
@@ -430,8 +439,17 @@ class RMNet(nn.Module):
 
         # ---- clip-level bookkeeping, hoisted out of the frame loop (the only host syncs)
         if plans is not None:                   # (none here: the plans were made from one download of the presence words)
-            if len(plans) != B or tuple(labels_dev.shape) != (B, N, H, W) or labels_dev.dtype != torch.uint8 or labels_dev.device != dev \
-                    or any(p.K != K or len(p.n_objects) != N for p in plans):
+            if sampling is not None:
+                from . import tta
+                fs, flips = float(sampling[0]), [bool(f) for f in sampling[1]]
+                if labels_dev.dim() != 4 or tuple(labels_dev.shape[:2]) != (B, N) or len(flips) != B or B > 64 \
+                        or tta.scaled_size(labels_dev.shape[2], labels_dev.shape[3], fs) != (H, W):
+                    raise RuntimeError('object_plan with sampling (fs, flips) must hold full-size labels [B, N, Hs, Ws] whose size scaled by '
+                                       'fs is the frames\', and one flip flag per batch slot (B <= 64)')
+                step = tta.scale_for_factor(fs)
+                sampling = (step, step, flips)
+            if len(plans) != B or (sampling is None and tuple(labels_dev.shape) != (B, N, H, W)) or labels_dev.dtype != torch.uint8 \
+                    or labels_dev.device != dev or any(p.K != K or len(p.n_objects) != N for p in plans):
                 raise RuntimeError('object_plan must be (uint8 labels [B, N, H, W] on the device, one plan of N frames and K planes per clip)')
             n_max = [p.n_max for p in plans]
             fresh = set().union(*[p.fresh for p in plans])
@@ -476,7 +494,7 @@ class RMNet(nn.Module):
             if plans is not None:
                 if t in edited:     # models/rmnet.py:436-450 in one launch, written straight into est[:, t]
                     logit = logit.contiguous()
-                    ops.object_edit_softmax(logit, labels_dev[:, t] if t in inject else None, lut_dev, action_dev[t], est[:, t])
+                    ops.object_edit_softmax(logit, labels_dev[:, t] if t in inject else None, lut_dev, action_dev[t], est[:, t], sampling)
                 else:
                     est[:, t] = F.softmax(logit, dim=1) if prob is None else prob
                 if return_logits:

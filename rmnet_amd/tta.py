@@ -14,6 +14,7 @@ returns the same bits.
 
 import math
 
+import numpy as np
 import torch
 
 from . import clip_io
@@ -39,6 +40,20 @@ def scaled_size(h, w, fs):
 def scale_for_factor(fs):
     """The source step per output pixel that F.interpolate(scale_factor=fs) hands its kernel: (float)(1.0 / fs)."""
     return _f32(1.0 / float(fs))
+
+
+def nearest_index_for_scale(out, inp, scale):
+    """The source index of every output index d = 0 .. out - 1 of an axis with ``inp`` elements, int64 numpy array:
+    min(int(floorf(float(d) * scale)), inp - 1) with the product rounded to float32 (include/rmnet_hip.h I2).  Host only."""
+    d = np.arange(int(out), dtype=np.float32)
+    return np.minimum(np.floor(d * np.float32(scale)), np.float32(int(inp) - 1)).astype(np.int64)
+
+
+def nearest_index(out, inp, fs):
+    """``nearest_index_for_scale`` with the scale of F.interpolate(scale_factor=fs, mode='nearest'), (float)(1.0 / fs): torch's
+    legacy nearest rule as a plain formula.  torch's CPU kernels copy an axis whose output size equals its input size or its
+    double even when ``fs`` is neither 1 nor 2; this does not."""
+    return nearest_index_for_scale(out, inp, scale_for_factor(fs))
 
 
 def _axis(out, inp, scale, device):

@@ -13,7 +13,17 @@
            three timed calls each, alternating, host clock around a device synchronise; torch.cuda.max_memory_allocated above what
            is live before the call.  The label maps of the two routes are compared.
 
+  --scales the same clip under multi-scale and flipped inference, scales (0.75, 1.0, 1.25) + flip (include/rmnet_hip.h I2):
+           scaled_kernels  rmnet_label_presence_nearest_u8 over the three scales in one launch against rmnet_label_presence_u8 on
+                           three materialised nearest-resized clips (the resizes are timed apart), and
+                           rmnet_object_edit_softmax_nearest_f32 against rmnet_object_edit_softmax_f32 on a materialised, mirrored
+                           map, at the 0.75 scale; the results are compared.
+           scaled_call     segment_video_tta(new_objects=True), paired and unpaired, against helpers.multi_scale_inference fed the
+                           one-hot masks of all frames and the per-frame counts, followed by argmax_labels; for scale,
+                           segment_video_tta without late objects on the same frames.  Timed and compared as in ``call``.
+
     python tools/late_objects_bench.py            # every step in a child process of its own, under a time limit
+    python tools/late_objects_bench.py --scales
 
 The driver stops at the first step that does not return 0: nothing is started on the GPU after a step that failed there.
 """
@@ -33,6 +43,8 @@ N_MAX_OBJECTS = 10
 APPEARS_AT = 20
 MEAN, STD = (0.485, 0.456, 0.406), (0.229, 0.224, 0.225)
 STEPS = (('kernels', 300), ('call', 900))      # (step, time limit in seconds)
+SCALED_STEPS = (('scaled_kernels', 300), ('scaled_call', 1100))
+SCALES = (0.75, 1.0, 1.25)
 RUNS = 3
 
 
@@ -191,14 +203,144 @@ def step_call():
     torch.cuda.synchronize()
 
 
+def _resized_labels(torch, tta, labels, fs):
+    """The label maps nearest-resized by ``fs`` with the rule of the kernels, materialised."""
+    h, w = tta.scaled_size(H, W, fs)
+    iy = torch.from_numpy(tta.nearest_index(h, H, fs)).to(labels.device)
+    ix = torch.from_numpy(tta.nearest_index(w, W, fs)).to(labels.device)
+    return labels.index_select(1, iy).index_select(2, ix).contiguous()
+
+
+def step_scaled_kernels():
+    import torch
+    from rmnet_amd import object_plan, ops, tta
+    assert torch.cuda.is_available(), 'this step needs a GPU'
+    dev = torch.device('cuda', 0)
+    _, labels = _clip(torch)
+    labels = labels.to(dev)
+    K = N_MAX_OBJECTS + 1
+    sizes = [tta.scaled_size(H, W, fs) for fs in SCALES]
+    steps = [(tta.scale_for_factor(fs),) * 2 for fs in SCALES]
+    resized = [_resized_labels(torch, tta, labels, fs) for fs in SCALES]
+    plans = object_plan.appearance_plans(ops.label_presence(labels), ops.label_presence_nearest(labels, sizes, steps), N_MAX_OBJECTS)
+    fs, (h, w), step, plan, t = SCALES[0], sizes[0], steps[0][0], plans[0], APPEARS_AT
+    gen = torch.Generator(device=dev).manual_seed(0)
+    logit0 = torch.randn(2, K, h, w, device=dev, generator=gen) * 4.0
+    action = plan.action[t:t + 1].expand(2, -1).contiguous()
+    lut = plan.lut[None].expand(2, -1).contiguous()
+    full = labels[t:t + 1].expand(2, -1, -1)
+    small = torch.stack([resized[0][t], torch.flip(resized[0][t], dims=[1])])
+    logit, prob, prob_m = logit0.clone(), torch.empty(2, K, h, w, device=dev), torch.empty(2, K, h, w, device=dev)
+
+    def sampling_edit():
+        logit.copy_(logit0)
+        return ops.object_edit_softmax(logit, full, lut, action, prob, sampling=(step, step, (False, True)))
+
+    def materialised_edit():
+        logit.copy_(logit0)
+        return ops.object_edit_softmax(logit, small, lut, action, prob_m)
+
+    print('%d label maps of %d x %d at the scales %s; a pair of frames (one mirrored) of K = %d logits at %d x %d with actions %s; median of '
+          '20 calls between device events (10 %% .. 90 %%)' % (N, W, H, SCALES, K, w, h, plan.action_host[t].tolist()))
+    print('| step | ms per call | 10 % .. 90 % |')
+    print('|---|---|---|')
+    for name, fn in (('rmnet_label_presence_nearest_u8, %d frames x 3 scales, one launch' % N, lambda: ops.label_presence_nearest(labels, sizes, steps)),
+                     ('  rmnet_label_presence_u8 on three materialised resized clips', lambda: [ops.label_presence(r) for r in resized]),
+                     ('  (materialising the three resized clips with torch indexing)', lambda: [_resized_labels(torch, tta, labels, f) for f in SCALES]),
+                     ('rmnet_object_edit_softmax_nearest_f32, B = 2 (+ the copy that restores the logits)', sampling_edit),
+                     ('  rmnet_object_edit_softmax_f32 on the materialised, mirrored maps (+ the copy)', materialised_edit),
+                     ('  (the copy alone)', lambda: logit.copy_(logit0))):
+        med, lo, hi = _median_ms(torch, fn)
+        print('| %s | %.3f | %.3f .. %.3f |' % (name, med, lo, hi))
+    same_words = all(torch.equal(a, ops.label_presence(r)) for a, r in zip(ops.label_presence_nearest(labels, sizes, steps), resized))
+    sampling_edit()
+    lg = logit.clone()
+    materialised_edit()
+    print('presence: every word equal to that of the materialised clips: %s; edit: logits equal in every bit: %s, probabilities equal in '
+          'every bit: %s' % (same_words, bool(torch.equal(lg.view(torch.int32), logit.view(torch.int32))),
+                             bool(torch.equal(prob.view(torch.int32), prob_m.view(torch.int32)))))
+    torch.cuda.synchronize()
+
+
+def step_scaled_call():
+    from types import SimpleNamespace
+    import torch
+    from rmnet_amd import clip_io, helpers, inference, networks
+    from rmnet_amd.rmnet import RMNet
+    from rmnet_amd.tiny_flownet import TinyFlowNet
+    assert torch.cuda.is_available(), 'this step needs a GPU'
+    dev = torch.device('cuda', 0)
+    u8, labels = _clip(torch)
+    u8, labels = u8.to(dev), labels.to(dev)
+    K = N_MAX_OBJECTS + 1
+    frames = clip_io.normalize_frames(u8, MEAN, STD)
+    cfg = SimpleNamespace(TEST=SimpleNamespace(FRAME_SCALES=list(SCALES), FLIP_LR=True, MEMORIZE_EVERY=5))
+
+    def planned(pair):
+        return lambda net, tfn: inference.segment_video_tta(net, tfn, {'frames': frames, 'labels': labels}, SCALES, True, 5, pair_flips=pair,
+                                                            new_objects=True, n_max_objects=N_MAX_OBJECTS)['labels']
+
+    def unplanned(net, tfn):
+        present = scatter_presence(torch, labels).cpu()                     # the per-frame counts of utils/data_loaders.py:58-65
+        present[:, 255] = 0
+        counts = (torch.cummax(present, dim=0).values.sum(dim=1) - 1).clamp(max=N_MAX_OBJECTS)
+        lut, _ = clip_io.reorganize_lut(labels)
+        masks = clip_io.onehot_labels(labels, K, lut)
+        _, probs = helpers.multi_scale_inference(cfg, tfn, net, frames.unsqueeze(0), masks.unsqueeze(0), counts.view(1, N))
+        return clip_io.argmax_labels(probs[0].contiguous())
+
+    def no_late_objects(net, tfn):
+        lut, _ = clip_io.reorganize_lut(labels)
+        masks = clip_io.onehot_labels(labels[:1], K, lut).expand(N, -1, -1, -1)
+        return inference.segment_video_tta(net, tfn, {'frames': frames, 'masks': masks, 'n_objects': 2}, SCALES, True, 5)['labels']
+
+    print('%d frames of %d x %d, n_max_objects = %d, object 2 from frame %d, scales %s + flip; seconds per call, host clock around a device '
+          'synchronise, %d timed calls each after one warm-up call each, alternating' % (N, W, H, N_MAX_OBJECTS, APPEARS_AT, SCALES, RUNS))
+    print('| network | route | seconds per call (each run) | median | peak MB above the inputs |')
+    print('|---|---|---|---|---|')
+    for fused in (False, True):
+        net = networks.procedural_init_(RMNet(None)).to(dev).eval()
+        tfn = networks.procedural_init_(TinyFlowNet(None)).to(dev).eval()
+        if fused:
+            net.fuse_epilogues()
+        variants = (('segment_video_tta(new_objects=True), paired flips', planned(True)),
+                    ('segment_video_tta(new_objects=True), unpaired', planned(False)),
+                    ('helpers.multi_scale_inference, one-hot masks of all frames + per-frame counts + argmax_labels', unplanned),
+                    ('(segment_video_tta without late objects: object 2 counted from frame 0)', no_late_objects))
+        times, peaks, results = {n: [] for n, _ in variants}, {}, {}
+        with torch.no_grad():
+            for name, fn in variants:
+                peaks[name], out = _peak_mb(torch, lambda: fn(net, tfn))
+                del out
+            for _ in range(RUNS):
+                for name, fn in variants:
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                    out = fn(net, tfn)
+                    torch.cuda.synchronize()
+                    times[name].append(time.perf_counter() - t0)
+                    results[name] = out
+                    del out
+        for name, _ in variants:
+            print('| %s | %s | %s | %.3f | %.0f |' % ('fuse_epilogues()' if fused else 'module graph', name, ', '.join('%.3f' % t for t in times[name]),
+                                                   statistics.median(times[name]), peaks[name]))
+        want = results[variants[2][0]]
+        for name in (variants[0][0], variants[1][0]):
+            a = results[name]
+            print('  %s: label maps equal to multi_scale_inference\'s at %.6f of the pixels; pixels of object 2 before / from frame %d: %d / %d'
+                  % (name, float((a == want).float().mean()), APPEARS_AT, int((a[:APPEARS_AT] == 2).sum()), int((a[APPEARS_AT:] == 2).sum())))
+    torch.cuda.synchronize()
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument('--step', choices=[s for s, _ in STEPS])
+    ap.add_argument('--step', choices=[s for s, _ in STEPS + SCALED_STEPS])
+    ap.add_argument('--scales', action='store_true', help='the steps under multi-scale and flipped inference')
     args = ap.parse_args()
     if args.step:
-        {'kernels': step_kernels, 'call': step_call}[args.step]()
+        {'kernels': step_kernels, 'call': step_call, 'scaled_kernels': step_scaled_kernels, 'scaled_call': step_scaled_call}[args.step]()
         return 0
-    for step, limit in STEPS:
+    for step, limit in (SCALED_STEPS if args.scales else STEPS):
         try:
             rc = subprocess.run([sys.executable, os.path.abspath(__file__), '--step', step], timeout=limit).returncode
         except subprocess.TimeoutExpired:
