@@ -56,116 +56,38 @@
 //   registers      weights 2 sets x 4 fragments x 4 VGPRs (this step's, the next step's), activations' prefetch 8, X fragments 16
 //   MFMA           per wave 8 x 2 tiles x 3 terms = 48, the same 1536 clk per step and SIMD; the ceiling above is unchanged.
 // Measured (profiles/r19_a_conv3x3_wreg.md): 4-7 % less time per call than conv3x3_split, the same bits.
-#include "split_f16.h"      // the vector types, kKT, kThreads, the activation scale, swz
+//
+// What the two kernels (and conv3x3_rows of csrc/conv3x3_rows.hip, which must return the same bits) have in common is written once,
+// in csrc/conv3x3_parts.h: ConvArgs and the argument rules, the per-tap activation loader (border bits, set_tap, the two loads, the
+// split into the X planes), the tap-class dispatch and the fp32 epilogue.  This file keeps what differs: the tile ownership, the
+// weights' way, mma() and the K loops with their fences and groups (profiles/r32_a_decoder_conv_fold.md).
+#include "conv3x3_parts.h"
 
 namespace rmnet {
 namespace {
 
-constexpr int kCout = 256;       // output channels (fixed)
-constexpr int kMT = 128;         // pixels per workgroup
 constexpr int kXPlane = kMT * kKT;                 // halves per activation plane
 constexpr int kWPlane = kCout * kKT;               // halves per weight plane
 constexpr int kBufHalves = 2 * kXPlane + 2 * kWPlane;
 static_assert(2 * kBufHalves * 2 <= kLdsBytesPerCU, "LDS budget");
-
-template <bool B>
-struct Flag {
-  static constexpr bool value = B;
-};
-
-struct ConvArgs {
-  const float* x;          // [M][Cin]
-  const half8* wp;         // [9 * Cin / 32][2][256][32] fp16
-  const float* w_unscale;  // [256]
-  const float* bias;       // [256] or null
-  const float* res;        // [M][256] or null
-  float* out;              // [M][256]
-  int* range;              // or null
-  int M, H, W, Cin, relu_in, relu_out;
-};
 
 __global__ __launch_bounds__(kThreads) void conv3x3_split(ConvArgs a) {
   __shared__ __attribute__((aligned(16))) _Float16 lds[2 * kBufHalves];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wm = wave & 1, wn = wave >> 1;
   const int m0 = blockIdx.x * kMT;
-  const int HW = a.H * a.W, CB = a.Cin / kKT;
+  const int CB = a.Cin / kKT;
 
-  // loader items: activations 2 x float4 per thread (pixel p = tid/8 + 64i, channels 4*(tid&7) ..),
-  // weights 4 x 16 B per thread (chunk q = tid + 512i of the step's 2048)
-  const int c4 = tid & 7;
-  int pm[2];               // the pixel (0 past M)
-  unsigned inside[2];      // bit t: tap t of this pixel lies inside the map (past M: none does) -- the border test, once per pixel
-#pragma unroll
-  for (int i = 0; i < 2; ++i) {
-    const int m = m0 + (tid >> 3) + 64 * i;
-    const bool pin = m < a.M;
-    pm[i] = pin ? m : 0;
-    const int r = pm[i] % HW;
-    const int ph = r / a.W, pw = r % a.W;
-    inside[i] = 0;
-#pragma unroll
-    for (int t = 0; t < 9; ++t) {
-      const int h = ph + t / 3 - 1, w = pw + t % 3 - 1;
-      inside[i] |= (pin && h >= 0 && h < a.H && w >= 0 && w < a.W ? 1u : 0u) << t;
-    }
-  }
-  f32x4 xr[2];
+  TapLoader ld{a};
+  ld.begin(tid, m0);
+  // weights: 4 x 16 B per thread (chunk q = tid + 512i of the step's 2048); per step their uniform base moves by one step's pack
   u32x4 wr[4];
-  int bad = 0;
-
-  // K is walked tap by tap, and inside a tap channel block by channel block.  What depends on the tap alone is set once per tap:
-  // whether the pixel's tap lies inside the map, and the address of its first channel block.  A tap outside the map reads the
-  // pixel itself instead (an address inside the tensor, whatever the tap) and the loaded values are replaced by zeros, so the load
-  // has no branch.  Per step only the two uniform bases move: the activations' by 32 channels, the weights' by one step's pack.
-  const float* xb = a.x;   // + the channel block (uniform)
-  unsigned xo[2];          // the tap's pixel x Cin + the thread's channels, in elements (M x Cin < 2^31)
-  bool in[2];
   const u32x4* wsrc = reinterpret_cast<const u32x4*>(a.wp);   // the step's pack (uniform)
-  auto set_tap = [&](int tap) {
-    const int d = (tap / 3 - 1) * a.W + (tap % 3 - 1);
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      in[i] = (inside[i] >> tap) & 1;
-      xo[i] = (unsigned)(pm[i] + (in[i] ? d : 0)) * a.Cin + 4 * c4;
-    }
-    xb = a.x;
-  };
   auto load = [&] {       // the next step's operands, activations first: the MFMA block waits for them alone half way
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      xr[i] = *reinterpret_cast<const f32x4*>(xb + xo[i]);
-    }
-    xb += kKT;
+    ld.load();
 #pragma unroll
     for (int i = 0; i < 4; ++i) wr[i] = wsrc[(unsigned)(tid + kThreads * i)];
     wsrc += 2 * kWPlane / 8;
-  };
-
-  // RELU: a.relu_in, CENTRE: the tap is the centre tap (the one that counts) -- both uniform over a tap, so the element loop has
-  // neither test
-  auto store_x = [&](auto relu, auto centre, _Float16* buf) __attribute__((always_inline)) {
-    _Float16* xh = buf;
-    _Float16* xl = buf + kXPlane;
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      half4 hi, lo;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        float v = in[i] ? xr[i][e] : 0.0f;
-        if constexpr (decltype(relu)::value) v = v < 0.0f ? 0.0f : v;          // (keeps NaN: it is counted below)
-        const float y = v * kActScale;
-        if constexpr (decltype(centre)::value) bad += !(fabsf(y) <= kF16Max) ? 1 : 0;
-        const float c = fminf(fmaxf(y, -kF16Max), kF16Max);   // NaN -> -65504 (saturated, counted)
-        const _Float16 h = (_Float16)c;
-        hi[e] = h;
-        lo[e] = (_Float16)(c - (float)h);
-      }
-      const int p = (tid >> 3) + 64 * i;
-      const int o = swz(p, c4 >> 1) + 4 * (c4 & 1);
-      *reinterpret_cast<half4*>(xh + o) = hi;
-      *reinterpret_cast<half4*>(xl + o) = lo;
-    }
   };
   auto store_w = [&](_Float16* buf) {
     _Float16* wb = buf + 2 * kXPlane;
@@ -185,12 +107,12 @@ __global__ __launch_bounds__(kThreads) void conv3x3_split(ConvArgs a) {
 #pragma unroll
     for (int j = 0; j < 4; ++j) acc[i][j] = accx[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-  set_tap(0);
+  ld.set_tap(0);
   load();
   if (a.relu_in)
-    store_x(Flag<true>{}, Flag<false>{}, lds);
+    ld.store<true, false>(lds);
   else
-    store_x(Flag<false>{}, Flag<false>{}, lds);
+    ld.store<false, false>(lds);
   store_w(lds);
   __syncthreads();
   const int fr = lane & 15, fc = lane >> 4;
@@ -237,7 +159,7 @@ __global__ __launch_bounds__(kThreads) void conv3x3_split(ConvArgs a) {
   auto run_taps = [&](auto relu, auto centre, int t0, int t1) __attribute__((always_inline)) {
 #pragma unroll 1
     for (int tap = t0; tap < t1; ++tap) {
-      if (tap) set_tap(tap);
+      if (tap) ld.set_tap(tap);
       const int n = tap ? CB : CB - 1;       // (tap 0's first block was the prologue's)
       for (int k = 0; k < n; ++k) {
         _Float16* nxt = lds + (par ^ 1) * kBufHalves;
@@ -245,7 +167,7 @@ __global__ __launch_bounds__(kThreads) void conv3x3_split(ConvArgs a) {
         __builtin_amdgcn_sched_barrier(0);
         mma(lds + par * kBufHalves, [&] {
           __builtin_amdgcn_sched_barrier(0);
-          store_x(relu, centre, nxt);
+          ld.store<decltype(relu)::value, decltype(centre)::value>(nxt);
         });
 #pragma unroll
         for (int g = 0; g < 24; ++g) {
@@ -259,76 +181,16 @@ __global__ __launch_bounds__(kThreads) void conv3x3_split(ConvArgs a) {
       }
     }
   };
-  // taps 0 .. 3, the centre tap, taps 5 .. 8: one after the other, and all of it once with and once without the input ReLU
-  auto run = [&](auto relu) __attribute__((always_inline)) {
-    run_taps(relu, Flag<false>{}, 0, 4);
-    run_taps(relu, Flag<true>{}, 4, 5);
-    run_taps(relu, Flag<false>{}, 5, 9);
-  };
-  if (a.relu_in)
-    run(Flag<true>{});
-  else
-    run(Flag<false>{});
+  run_tap_classes(a.relu_in, run_taps);
   mma(lds + par * kBufHalves, [] {});
 
-  // epilogue: D[co][px] -- lane holds pixel fr of each 16-pixel tile and the 4 consecutive channels 4*fc .. of each
-  // 16-channel tile, i.e. one float4 of NHWC memory per (tile pair).
-  // The residual: out may BE res, so the compiler keeps every read of res in front of the stores that follow it in the source.
-  // All 16 reads are therefore issued here, before the first store (one round trip, not 16 dependent ones; the loader's registers
-  // are dead by now).  This is safe with out == res: a thread reads exactly the elements it later writes, and no other thread
-  // touches them.
-  f32x4 r[4][4];
-  if (a.res) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int m = m0 + wm * 64 + i * 16 + fr;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const int co = wn * 64 + j * 16 + 4 * fc;
-        r[i][j] = m < a.M ? *reinterpret_cast<const f32x4*>(a.res + (size_t)m * kCout + co) : f32x4{0.f, 0.f, 0.f, 0.f};
-      }
-    }
-  }
-  // Unscale and shift in place, for all tiles, before the first store: for all the compiler knows these vectors alias out too, and
-  // read between the stores they would cost one more waited-for round trip per channel tile.
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const int co = wn * 64 + j * 16 + 4 * fc;
-    const f32x4 us = *reinterpret_cast<const f32x4*>(a.w_unscale + co) * kActUnscale;
-    const f32x4 b = a.bias ? *reinterpret_cast<const f32x4*>(a.bias + co) : f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int i = 0; i < 4; ++i) acc[i][j] = (acc[i][j] + accx[i][j]) * us + b;
-  }
-  // (An empty statement the optimiser cannot see through: without it the loop above is sunk into the guarded stores below, and
-  // each tile's wait for its unscale vector then includes the stores issued before it.)
-#pragma unroll
-  for (int j = 0; j < 4; ++j)
-#pragma unroll
-    for (int i = 0; i < 4; ++i) asm volatile("" : "+v"(acc[i][j]));
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const int co = wn * 64 + j * 16 + 4 * fc;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int m = m0 + wm * 64 + i * 16 + fr;
-      if (m >= a.M) continue;
-      const size_t off = (size_t)m * kCout + co;
-      f32x4 v = acc[i][j];
-      if (a.res) v += r[i][j];
-      if (a.relu_out) {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] = v[e] < 0.0f ? 0.0f : v[e];
-      }
-      *reinterpret_cast<f32x4*>(a.out + off) = v;
-    }
-  }
-  if (a.range && bad) atomicAdd(a.range, bad);
+  conv3x3_epilogue(a, acc, accx, m0 + wm * 64 + fr, wn * 64 + 4 * fc, ld.bad);   // pixels .. + 16i, channels .. + 16j ..
 }
 
 
 // ---------------------------------------------------------------------------------------------------------------- conv3x3_wreg
-// The same convolution with the weights kept out of LDS (the banner's last part).  Arguments, arithmetic, K order per accumulator
-// and epilogue expressions are conv3x3_split's, so outputs and range words are bit for bit the same; what differs is who owns what:
+// The same convolution with the weights kept out of LDS (the banner's last part).  Arguments, loader and epilogue are the shared
+// ones, arithmetic and K order per accumulator are conv3x3_split's, so outputs and range words are bit for bit the same; what differs:
 //   waves        the 8 waves divide the 256 output channels: wave w owns all 128 pixels x channels 32w .. 32w+31 = 8 x 2 MFMA tiles
 //                (still 48 MFMAs per wave and step, still 2 x 64 accumulator VGPRs).  No two waves need the same weight fragment.
 //   weights      the A fragment of one MFMA tile (16 channels x 32 of K of one plane) is 1 KB of contiguous pack memory, and lane
@@ -346,45 +208,10 @@ __global__ __launch_bounds__(kThreads) void conv3x3_wreg(ConvArgs a) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int fr = lane & 15, fc = lane >> 4;
   const int m0 = blockIdx.x * kMT;
-  const int HW = a.H * a.W, CB = a.Cin / kKT;
+  const int CB = a.Cin / kKT;
 
-  // activation loader: conv3x3_split's (pixel p = tid/8 + 64i, channels 4*(tid&7) ..)
-  const int c4 = tid & 7;
-  int pm[2];
-  unsigned inside[2];
-#pragma unroll
-  for (int i = 0; i < 2; ++i) {
-    const int m = m0 + (tid >> 3) + 64 * i;
-    const bool pin = m < a.M;
-    pm[i] = pin ? m : 0;
-    const int r = pm[i] % HW;
-    const int ph = r / a.W, pw = r % a.W;
-    inside[i] = 0;
-#pragma unroll
-    for (int t = 0; t < 9; ++t) {
-      const int h = ph + t / 3 - 1, w = pw + t % 3 - 1;
-      inside[i] |= (pin && h >= 0 && h < a.H && w >= 0 && w < a.W ? 1u : 0u) << t;
-    }
-  }
-  f32x4 xr[2];
-  int bad = 0;
-  const float* xb = a.x;
-  unsigned xo[2];
-  bool in[2];
-  auto set_tap = [&](int tap) {
-    const int d = (tap / 3 - 1) * a.W + (tap % 3 - 1);
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      in[i] = (inside[i] >> tap) & 1;
-      xo[i] = (unsigned)(pm[i] + (in[i] ? d : 0)) * a.Cin + 4 * c4;
-    }
-    xb = a.x;
-  };
-  auto load_x = [&] {
-#pragma unroll
-    for (int i = 0; i < 2; ++i) xr[i] = *reinterpret_cast<const f32x4*>(xb + xo[i]);
-    xb += kKT;
-  };
+  TapLoader ld{a};
+  ld.begin(tid, m0);
   // weight fragments [2 * channel tile + plane]: 16-byte chunk plane*1024 + co*4 + fc of the step's 2048, co = 32*wave + 16*j + fr
   half8 wa[4], wb[4];
   const half8* wsrc = a.wp;                                  // the step's pack (uniform)
@@ -396,29 +223,6 @@ __global__ __launch_bounds__(kThreads) void conv3x3_wreg(ConvArgs a) {
       for (int p = 0; p < 2; ++p) w[2 * j + p] = wsrc[wl + (unsigned)(p * (kWPlane / 8) + j * 64)];
     wsrc += 2 * kWPlane / 8;
   };
-  auto store_x = [&](auto relu, auto centre, _Float16* buf) __attribute__((always_inline)) {
-    _Float16* xh = buf;
-    _Float16* xl = buf + kXPlane;
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      half4 hi, lo;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        float v = in[i] ? xr[i][e] : 0.0f;
-        if constexpr (decltype(relu)::value) v = v < 0.0f ? 0.0f : v;          // (keeps NaN: it is counted below)
-        const float y = v * kActScale;
-        if constexpr (decltype(centre)::value) bad += !(fabsf(y) <= kF16Max) ? 1 : 0;
-        const float c = fminf(fmaxf(y, -kF16Max), kF16Max);   // NaN -> -65504 (saturated, counted)
-        const _Float16 h = (_Float16)c;
-        hi[e] = h;
-        lo[e] = (_Float16)(c - (float)h);
-      }
-      const int p = (tid >> 3) + 64 * i;
-      const int o = swz(p, c4 >> 1) + 4 * (c4 & 1);
-      *reinterpret_cast<half4*>(xh + o) = hi;
-      *reinterpret_cast<half4*>(xl + o) = lo;
-    }
-  };
 
   // acc[pixel tile][channel tile]: hi*hi, and the two cross terms, as in conv3x3_split
   f32x4 acc[8][2], accx[8][2];
@@ -427,13 +231,13 @@ __global__ __launch_bounds__(kThreads) void conv3x3_wreg(ConvArgs a) {
 #pragma unroll
     for (int j = 0; j < 2; ++j) acc[i][j] = accx[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-  set_tap(0);
-  load_x();
+  ld.set_tap(0);
+  ld.load();
   load_w(wa);
   if (a.relu_in)
-    store_x(Flag<true>{}, Flag<false>{}, lds);
+    ld.store<true, false>(lds);
   else
-    store_x(Flag<false>{}, Flag<false>{}, lds);
+    ld.store<false, false>(lds);
   __syncthreads();
   // One pixel tile at a time: its hi / lo fragments, then its six MFMAs -- per accumulator Ah*Bh, then Ah*Bl, then Al*Bh, which is
   // conv3x3_split's order.  (The swizzle term of a fragment's address depends on fr alone: the eight tiles are 1 KB apart.)
@@ -465,13 +269,13 @@ __global__ __launch_bounds__(kThreads) void conv3x3_wreg(ConvArgs a) {
   int par = 0;
   auto step = [&](auto relu, auto centre, const half8(&wc)[4], half8(&wn)[4]) __attribute__((always_inline)) {
     _Float16* nxt = lds + (par ^ 1) * kXBufHalves;
-    load_x();
+    ld.load();
     __builtin_amdgcn_sched_barrier(0);     // (activations first: the split half way waits for them alone, by count)
     load_w(wn);
     __builtin_amdgcn_sched_barrier(0);
     mma(lds + par * kXBufHalves, wc, [&] {
       __builtin_amdgcn_sched_barrier(0);
-      store_x(relu, centre, nxt);
+      ld.store<decltype(relu)::value, decltype(centre)::value>(nxt);
     });
 #pragma unroll
     for (int g = 0; g < 24; ++g) {
@@ -486,7 +290,7 @@ __global__ __launch_bounds__(kThreads) void conv3x3_wreg(ConvArgs a) {
   auto run_taps = [&](auto relu, auto centre, int t0, int t1) __attribute__((always_inline)) {
 #pragma unroll 1
     for (int tap = t0; tap < t1; ++tap) {
-      if (tap) set_tap(tap);
+      if (tap) ld.set_tap(tap);
       const int n = tap ? CB : CB - 1;       // (tap 0's first block was the prologue's)
       int k = 0;
 #pragma unroll 1
@@ -501,91 +305,19 @@ __global__ __launch_bounds__(kThreads) void conv3x3_wreg(ConvArgs a) {
       }
     }
   };
-  auto run = [&](auto relu) __attribute__((always_inline)) {
-    run_taps(relu, Flag<false>{}, 0, 4);
-    run_taps(relu, Flag<true>{}, 4, 5);
-    run_taps(relu, Flag<false>{}, 5, 9);
-  };
-  if (a.relu_in)
-    run(Flag<true>{});
-  else
-    run(Flag<false>{});
+  run_tap_classes(a.relu_in, run_taps);
   mma(lds + par * kXBufHalves, wa, [] {});
 
-  // epilogue: conv3x3_split's, with pixel m0 + 16i + fr and channels 32*wave + 16j + 4*fc ..
-  f32x4 r[8][2];
-  if (a.res) {
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      const int m = m0 + i * 16 + fr;
-#pragma unroll
-      for (int j = 0; j < 2; ++j) {
-        const int co = wave * 32 + j * 16 + 4 * fc;
-        r[i][j] = m < a.M ? *reinterpret_cast<const f32x4*>(a.res + (size_t)m * kCout + co) : f32x4{0.f, 0.f, 0.f, 0.f};
-      }
-    }
-  }
-#pragma unroll
-  for (int j = 0; j < 2; ++j) {
-    const int co = wave * 32 + j * 16 + 4 * fc;
-    const f32x4 us = *reinterpret_cast<const f32x4*>(a.w_unscale + co) * kActUnscale;
-    const f32x4 b = a.bias ? *reinterpret_cast<const f32x4*>(a.bias + co) : f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int i = 0; i < 8; ++i) acc[i][j] = (acc[i][j] + accx[i][j]) * us + b;
-  }
-#pragma unroll
-  for (int j = 0; j < 2; ++j)
-#pragma unroll
-    for (int i = 0; i < 8; ++i) asm volatile("" : "+v"(acc[i][j]));
-#pragma unroll
-  for (int j = 0; j < 2; ++j) {
-    const int co = wave * 32 + j * 16 + 4 * fc;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      const int m = m0 + i * 16 + fr;
-      if (m >= a.M) continue;
-      const size_t off = (size_t)m * kCout + co;
-      f32x4 v = acc[i][j];
-      if (a.res) v += r[i][j];
-      if (a.relu_out) {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] = v[e] < 0.0f ? 0.0f : v[e];
-      }
-      *reinterpret_cast<f32x4*>(a.out + off) = v;
-    }
-  }
-  if (a.range && bad) atomicAdd(a.range, bad);
+  conv3x3_epilogue(a, acc, accx, m0 + fr, wave * 32 + 4 * fc, ld.bad);      // pixels m0 + 16i + fr, channels 32*wave + 16j + 4*fc ..
 }
 
-}  // namespace
-}  // namespace rmnet
-
-namespace rmnet {
-namespace {
-
-// both entries: the same argument rules, one kernel each
+// both entries: the argument rules of conv3x3_parts.h, one kernel each
 int conv3x3_launch(void (*kernel)(ConvArgs), const float* x, const void* wpack, const float* w_unscale, const float* bias,
                    const float* res, int flags, int N, int H, int W, int Cin, float* out, int32_t* range_word, void* stream) {
-  if (!x || !wpack || !w_unscale || !out || N <= 0 || H <= 0 || W <= 0 || Cin <= 0) return RMNET_E_INVALID_ARG;
-  if (flags & ~(RMNET_CONV_RELU_IN | RMNET_CONV_RELU_OUT)) return RMNET_E_INVALID_ARG;
-  if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(wpack) | reinterpret_cast<uintptr_t>(w_unscale) |
-       reinterpret_cast<uintptr_t>(bias) | reinterpret_cast<uintptr_t>(res) | reinterpret_cast<uintptr_t>(out)) & 15)
-    return RMNET_E_INVALID_ARG;
-  if (Cin % kKT) return RMNET_E_UNSUPPORTED;
-  const long long M = (long long)N * H * W;
-  if (M * (long long)(Cin > kCout ? Cin : kCout) >= (1LL << 31)) return RMNET_E_UNSUPPORTED;   // (int pixel index, size_t offsets)
-  // out must not overlap x (other workgroups read x's halo); it may BE res: each element is read, then written, by one thread.  The
-  // epilogue reads all of a thread's residual values before its first store; a thread reads exactly the elements it later writes
-  // and no other thread touches them, so that is safe as well
-  const char* xb = reinterpret_cast<const char*>(x);
-  const char* ob = reinterpret_cast<const char*>(out);
-  if (ob < xb + M * Cin * sizeof(float) && xb < ob + M * kCout * sizeof(float)) return RMNET_E_INVALID_ARG;
   ConvArgs a;
-  a.x = x; a.wp = reinterpret_cast<const half8*>(wpack); a.w_unscale = w_unscale; a.bias = bias; a.res = res; a.out = out;
-  a.range = range_word; a.M = (int)M; a.H = H; a.W = W; a.Cin = Cin;
-  a.relu_in = (flags & RMNET_CONV_RELU_IN) != 0;
-  a.relu_out = (flags & RMNET_CONV_RELU_OUT) != 0;
-  hipLaunchKernelGGL(kernel, dim3((unsigned)((M + kMT - 1) / kMT)), dim3(kThreads), 0, (hipStream_t)stream, a);
+  const int rc = conv3x3_args(a, x, wpack, w_unscale, bias, res, flags, N, H, W, Cin, out, range_word);
+  if (rc != RMNET_OK) return rc;
+  hipLaunchKernelGGL(kernel, dim3((unsigned)((a.M + kMT - 1) / kMT)), dim3(kThreads), 0, (hipStream_t)stream, a);
   return check_launch();
 }
 

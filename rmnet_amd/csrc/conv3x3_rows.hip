@@ -9,44 +9,28 @@
 // activation load, a split, an LDS write or a barrier: six barriers per workgroup instead of 72.
 //
 // What this file adds to the engine:
-//   * staging from fp32: the per-element expression of conv3x3_wreg's loader (optional ReLU, * 64, range test, clamp, hi = fp16(c),
+//   * staging from fp32: the per-element expression of the per-tap loader (optional ReLU, * 64, range test, clamp, hi = fp16(c),
 //     lo = fp16(c - hi)) without its border select (the engine masks at the fragment reads).  The range count is taken while the
 //     centre row (dy = 0) is staged, for the workgroup's own pixels only: each element once.  The staging writes (ds_write_b64:
-//     groups of 16 lanes = 2 consecutive rows x 64 B) are conflict-free under the engine's swizzle;
-//   * the epilogue tail: conv3x3_wreg's residual, ReLU and fp32 store.
+//     groups of 16 lanes = 2 consecutive rows x 64 B) are conflict-free under the engine's swizzle.
+// The argument struct, the argument rules and the epilogue (residual, ReLU, fp32 store, range word) are conv3x3.hip's kernels' own
+// text: csrc/conv3x3_parts.h.
 // Only Cin = 256 fits with the K order kept (Cin = 512 would need 266 KB); other shapes stay on conv3x3.hip's kernels.
 // Measured: profiles/r20_a_conv3x3_rows.md.
+#include "conv3x3_parts.h"
 #include "conv_rows_core.h"
 
 namespace rmnet {
 namespace {
 
-constexpr int kCout = 256;       // output channels (fixed)
 constexpr int kCin = 256;        // input channels (fixed: the row image is sized for it)
-constexpr int kMT = 128;         // pixels per workgroup
 constexpr int kRowsLdsBytes = rows_image_bytes(kCin, kMT);
 static_assert(kRowsLdsBytes == 137216, "8 blocks x 2 planes x 134 rows x 64 B");
 static_assert(kRowsLdsBytes <= kLdsBytesPerCU, "LDS budget");
 constexpr int kStageBatch = 8;                     // staging loads in flight per thread before the first split (16: the same time)
 constexpr int kStagePasses = kMT / 8;              // full staging passes: 8 rows x 256 channels per pass and workgroup
 
-template <bool B>
-struct Flag {
-  static constexpr bool value = B;
-};
-
-struct RowsArgs {
-  const float* x;          // [M][256]
-  const half8* wp;         // [72][2][256][32] fp16
-  const float* w_unscale;  // [256]
-  const float* bias;       // [256] or null
-  const float* res;        // [M][256] or null
-  float* out;              // [M][256]
-  int* range;              // or null
-  int M, H, W, relu_in, relu_out;
-};
-
-__global__ __launch_bounds__(kThreads) void conv3x3_rows(RowsArgs a) {
+__global__ __launch_bounds__(kThreads) void conv3x3_rows(ConvArgs a) {
   using Core = RowsCore<kCin, kMT>;
   constexpr int kPlaneHalves = Core::kPlaneHalves, kBlockHalves = Core::kBlockHalves;
   _Float16* const lds = rows_lds;
@@ -54,7 +38,6 @@ __global__ __launch_bounds__(kThreads) void conv3x3_rows(RowsArgs a) {
   const int m0 = blockIdx.x * kMT;
   Core core;
   core.begin(tid, wave, 0, m0, a.wp, a.M, a.H, a.W);
-  const int fr = core.fr, fc = core.fc;
 
   // staging items: thread -> (row 2 * (tid / 128) + (tid / 8) % 2 of each pass of 8 rows, channel block (tid / 16) % 8, channels
   // 4 * (tid % 8) .. of it): 8 lanes read 128 contiguous bytes, 16 lanes write two consecutive 64-byte LDS rows
@@ -119,41 +102,10 @@ __global__ __launch_bounds__(kThreads) void conv3x3_rows(RowsArgs a) {
     for (int tx = 0; tx < 3; ++tx) core.run_tap(3 * ty + tx);
   }
 
-  // epilogue: conv3x3_wreg's, expression for expression (pixel m0 + 16i + fr, channels 32*wave + 16j + 4*fc ..).  All residual
-  // reads come before the first store: out may BE res
+  // the epilogue: pixels m0 + 16i + fr, channels 32*wave + 16j + 4*fc ..
   int me = m0;                                               // (opaque: the pixel indices are formed again here; taken from the
   asm volatile("" : "+s"(me));                               // mask computation they stay live across the K loop and spill)
-  f32x4 r[8][2];
-  if (a.res) {
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      const int m = me + i * 16 + fr;
-#pragma unroll
-      for (int j = 0; j < 2; ++j) {
-        const int co = wave * 32 + j * 16 + 4 * fc;
-        r[i][j] = m < a.M ? *reinterpret_cast<const f32x4*>(a.res + (size_t)m * kCout + co) : f32x4{0.f, 0.f, 0.f, 0.f};
-      }
-    }
-  }
-  core.unscale_shift(a.w_unscale, a.bias, wave);
-#pragma unroll
-  for (int j = 0; j < 2; ++j) {
-    const int co = wave * 32 + j * 16 + 4 * fc;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      const int m = me + i * 16 + fr;
-      if (m >= a.M) continue;
-      const size_t off = (size_t)m * kCout + co;
-      f32x4 v = core.acc[i][j];
-      if (a.res) v += r[i][j];
-      if (a.relu_out) {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] = v[e] < 0.0f ? 0.0f : v[e];
-      }
-      *reinterpret_cast<f32x4*>(a.out + off) = v;
-    }
-  }
-  if (a.range && bad) atomicAdd(a.range, bad);
+  conv3x3_epilogue(a, core.acc, core.accx, me + core.fr, wave * 32 + 4 * core.fc, bad);
 }
 
 }  // namespace
@@ -162,26 +114,12 @@ __global__ __launch_bounds__(kThreads) void conv3x3_rows(RowsArgs a) {
 extern "C" int rmnet_conv3x3_rows_f32(const float* x, const void* wpack, const float* w_unscale, const float* bias, const float* res,
                                       int flags, int N, int H, int W, int Cin, float* out, int32_t* range_word, void* stream) {
   using namespace rmnet;
-  // rmnet_conv3x3_split_f32's rules (conv3x3.hip: conv3x3_launch), then Cin
-  if (!x || !wpack || !w_unscale || !out || N <= 0 || H <= 0 || W <= 0 || Cin <= 0) return RMNET_E_INVALID_ARG;
-  if (flags & ~(RMNET_CONV_RELU_IN | RMNET_CONV_RELU_OUT)) return RMNET_E_INVALID_ARG;
-  if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(wpack) | reinterpret_cast<uintptr_t>(w_unscale) |
-       reinterpret_cast<uintptr_t>(bias) | reinterpret_cast<uintptr_t>(res) | reinterpret_cast<uintptr_t>(out)) & 15)
-    return RMNET_E_INVALID_ARG;
-  if (Cin % kKT) return RMNET_E_UNSUPPORTED;
-  const long long M = (long long)N * H * W;
-  if (M * (long long)(Cin > kCout ? Cin : kCout) >= (1LL << 31)) return RMNET_E_UNSUPPORTED;   // (int pixel index, size_t offsets)
-  const char* xb = reinterpret_cast<const char*>(x);
-  const char* ob = reinterpret_cast<const char*>(out);
-  if (ob < xb + M * Cin * sizeof(float) && xb < ob + M * kCout * sizeof(float)) return RMNET_E_INVALID_ARG;
-  if (Cin != kCin) return RMNET_E_UNSUPPORTED;              // the row image holds exactly 256 channels
-  const int rc = rows_prepare<conv3x3_rows, kRowsLdsBytes>((hipStream_t)stream);
+  ConvArgs a;
+  int rc = conv3x3_args(a, x, wpack, w_unscale, bias, res, flags, N, H, W, Cin, out, range_word);
   if (rc != RMNET_OK) return rc;
-  RowsArgs a;
-  a.x = x; a.wp = reinterpret_cast<const half8*>(wpack); a.w_unscale = w_unscale; a.bias = bias; a.res = res; a.out = out;
-  a.range = range_word; a.M = (int)M; a.H = H; a.W = W;
-  a.relu_in = (flags & RMNET_CONV_RELU_IN) != 0;
-  a.relu_out = (flags & RMNET_CONV_RELU_OUT) != 0;
-  hipLaunchKernelGGL(conv3x3_rows, dim3((unsigned)((M + kMT - 1) / kMT)), dim3(kThreads), kRowsLdsBytes, (hipStream_t)stream, a);
+  if (Cin != kCin) return RMNET_E_UNSUPPORTED;              // the row image holds exactly 256 channels
+  rc = rows_prepare<conv3x3_rows, kRowsLdsBytes>((hipStream_t)stream);
+  if (rc != RMNET_OK) return rc;
+  hipLaunchKernelGGL(conv3x3_rows, dim3((unsigned)((a.M + kMT - 1) / kMT)), dim3(kThreads), kRowsLdsBytes, (hipStream_t)stream, a);
   return check_launch();
 }

@@ -15,8 +15,8 @@
 //   * steps run in (tap 0..8, channel block 0..C/32-1) order; per step and pixel tile Ah*Wh into acc, then Ah*Wl, then Al*Wh into
 //     accx: every accumulator sees the same operands in the same order, whatever the wave layout;
 //   * the weight fragments go straight from the pack into two alternating register sets, one step ahead, no weight LDS;
-//   * the per-element split (split4) and the epilogue head are those kernels', expression for expression;
-//   * the border test moved, its result did not.  The per-tap loaders replace the value of a tap outside the map by zero before the
+//   * the per-element split (split4) and the epilogue head (unscale_shift) are the ones of split_f16.h;
+//   * the border test (taps_inside, split_f16.h) moved, its result did not.  The per-tap loaders replace the value of a tap outside the map by zero before the
 //     split; here a staged row serves three taps of different pixels (the row that is the dx = 0 tap of one pixel is the row-wrap
 //     neighbour for dx = -1 of the next), so the staged rows are never masked.  Instead each lane selects, once per (pixel tile, tap),
 //     the LDS row it reads: the real row, or one of the plane's rows of zeros -- the same +0.0 operand bits.  Staged pixels outside
@@ -78,22 +78,9 @@ struct RowsCore {
     if (tid < 16 * 2 * kCB) *reinterpret_cast<half8*>(rows_lds + (tid >> 4) * kPlaneHalves + kStaged * kKT + 8 * (tid & 15)) = half8{0, 0, 0, 0, 0, 0, 0, 0};
     // the border test, once per pixel: bit t of pixel tile i's 9 bits = tap t of pixel m1 + 16i + fr lies inside the map (past M: none
     // does) -- the per-tap loaders' test, for the pixels whose fragments this lane reads; three tiles per register
-    const int HW = H * W;
     inside[0] = inside[1] = inside[2] = 0u;
 #pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      const int m = m1 + 16 * i + fr;
-      const bool pin = m < M;
-      const int r = (pin ? m : 0) % HW;
-      const int ph = r / W, pw = r % W;
-      unsigned bits = 0;
-#pragma unroll
-      for (int t = 0; t < 9; ++t) {
-        const int h = ph + t / 3 - 1, w = pw + t % 3 - 1;
-        bits |= (pin && h >= 0 && h < H && w >= 0 && w < W ? 1u : 0u) << t;
-      }
-      inside[i / 3] |= bits << (9 * (i % 3));
-    }
+    for (int i = 0; i < 8; ++i) inside[i / 3] |= taps_inside(m1 + 16 * i + fr, M, H, W) << (9 * (i % 3));
     wsrc = wp;
     wlast = wp + (9 * kCB - 1) * (2 * kWPlane / 8);
     wl = (wcol * 32 + fr) * 4 + fc;
@@ -170,21 +157,9 @@ struct RowsCore {
     __builtin_amdgcn_sched_barrier(0);
   }
 
-  // the epilogue's head: acc = (acc + accx) * unscale / 64 + shift for channels 32 wcol + 16 j + 4 fc ..; then opaque, so that the
-  // tail's loads and stores are not scheduled into it
+  // the epilogue's head (split_f16.h) for channels 32 wcol + 16 j + 4 fc ..
   __device__ __forceinline__ void unscale_shift(const float* unscale, const float* shift, int wcol) {
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      const int co = wcol * 32 + j * 16 + 4 * fc;
-      const f32x4 us = *reinterpret_cast<const f32x4*>(unscale + co) * kActUnscale;
-      const f32x4 b = shift ? *reinterpret_cast<const f32x4*>(shift + co) : f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int i = 0; i < 8; ++i) acc[i][j] = (acc[i][j] + accx[i][j]) * us + b;
-    }
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int i = 0; i < 8; ++i) asm volatile("" : "+v"(acc[i][j]));
+    rmnet::unscale_shift(acc, accx, unscale, shift, wcol * 32 + 4 * fc);
   }
 };
 

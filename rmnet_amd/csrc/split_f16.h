@@ -1,7 +1,8 @@
 // split_f16.h -- the vocabulary that every split-fp16 convolution kernel shares (conv3x3, conv3x3_rows, conv_split, conv_rows, stem,
 // flow_conv, flow_stem): the native vector types, the K step and workgroup size, the activation scale and fp16 window, the LDS swizzle
-// of the per-tap kernels, the per-element split, and the byte-range overlap test of the argument rules.  Nothing about a particular
-// kernel's tiles or row images belongs here (the tap-row engine's: conv_rows_core.h).
+// of the per-tap kernels, the per-element split, the 3x3 border test, the epilogue's head, and the byte-range overlap test of the
+// argument rules.  Nothing about a particular kernel's tiles or row images belongs here (the tap-row engine's: conv_rows_core.h; the
+// decoder kernels' loader, epilogue and argument rules: conv3x3_parts.h).
 #pragma once
 
 #include "common.h"
@@ -37,6 +38,41 @@ __device__ inline void split4(const f32x4 v, half4& hi, half4& lo, int& bad, int
     hi[e] = h;
     lo[e] = (_Float16)(c - (float)h);
   }
+}
+
+// The border test of a 3x3 / pad 1 kernel, once per pixel: bit t = tap t of pixel m (linear NHWC index) lies inside the H x W map; a
+// pixel past M has no tap inside.
+__device__ inline unsigned taps_inside(int m, int M, int H, int W) {
+  const bool pin = m < M;
+  const int r = (pin ? m : 0) % (H * W);
+  const int ph = r / W, pw = r % W;
+  unsigned bits = 0;
+#pragma unroll
+  for (int t = 0; t < 9; ++t) {
+    const int h = ph + t / 3 - 1, w = pw + t % 3 - 1;
+    bits |= (pin && h >= 0 && h < H && w >= 0 && w < W ? 1u : 0u) << t;
+  }
+  return bits;
+}
+
+// The epilogue's head for a lane's TI x TJ accumulator tiles: acc = (acc + accx) * unscale / 64 + shift for the channels cb + 16 j ..
+// (4 each), in place and for all tiles before the tail's first store: for all the compiler knows these vectors alias the output, and
+// read between the stores they would cost one more waited-for round trip per channel tile.  Then an empty statement the optimiser
+// cannot see through: without it the loop is sunk into the tail's guarded stores, and each tile's wait for its unscale vector then
+// includes the stores issued before it.
+template <int TI, int TJ>
+__device__ __forceinline__ void unscale_shift(f32x4 (&acc)[TI][TJ], const f32x4 (&accx)[TI][TJ], const float* unscale, const float* shift, int cb) {
+#pragma unroll
+  for (int j = 0; j < TJ; ++j) {
+    const f32x4 us = *reinterpret_cast<const f32x4*>(unscale + cb + 16 * j) * kActUnscale;
+    const f32x4 b = shift ? *reinterpret_cast<const f32x4*>(shift + cb + 16 * j) : f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int i = 0; i < TI; ++i) acc[i][j] = (acc[i][j] + accx[i][j]) * us + b;
+  }
+#pragma unroll
+  for (int j = 0; j < TJ; ++j)
+#pragma unroll
+    for (int i = 0; i < TI; ++i) asm volatile("" : "+v"(acc[i][j]));
 }
 
 inline bool overlap(const void* p, long long pn, const void* q, long long qn) {

@@ -35,7 +35,7 @@ import numpy as np
 import pytest
 import torch
 
-SHAPES = [(1, 1, 1, 32), (2, 5, 7, 32), (1, 9, 15, 96), (2, 8, 8, 160), (1, 12, 11, 64), (1, 3, 50, 256)]
+SHAPES = [(1, 1, 1, 32), (2, 5, 7, 32), (1, 9, 15, 96), (2, 8, 8, 160), (1, 12, 11, 64), (1, 3, 50, 256), (1, 2, 9, 1024)]
 GUARD = 64                     # floats in front of and behind the output (a multiple of 4: out stays 16-byte aligned)
 SENTINEL = -12345.5
 K_PER_BARRIER = 32             # conv3x3_wreg: K per step and barrier
