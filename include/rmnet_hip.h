@@ -710,6 +710,36 @@ int rmnet_object_edit_softmax_nearest_f32(float *logit, long long logit_batch_st
                                           unsigned long long flip_bits, const uint8_t *lut, const uint8_t *action, float *prob,
                                           long long prob_batch_stride, int B, int K, int H, int W, void *stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * I1  Validation loss of a clip: Lovasz-softmax brackets and the NLL sum (additive exports, same ABI version;
+ *     csrc/val_loss.hip).
+ * Replaces: lovasz_loss(est_probs, masks) + nll_loss(torch.log(est_probs), masks) of core/test.py:97 (models/lovasz_loss.py
+ *           and torch.nn.NLLLoss), without the reference's permuting copy, its sort of all pixels per class and its fp32 cumsums.
+ *   probs        [N,K,H,W] float32, 4-byte aligned (any alignment beyond that); labels [N,H,W] uint8 at any byte alignment.
+ *   ignore_index a label value 0 .. 255 whose pixels are left out; any other value: nothing is ignored.
+ *   bins         a power of two, 2 .. 2^22.
+ *   A pixel that is not ignored is BAD when its label is >= K (checked first) or when any of its K probabilities is not
+ *   inside [0, 1] (NaN included); bad pixels are counted and left out of everything.  For every other pixel and every class c:
+ *   fg = (label == c), e = fabsf((float)fg - p_c), key = (unsigned)(e * (float)bins) in [0, bins] (bin `bins` holds e == 1
+ *   alone), hist[c][fg][key] += 1, and nll_sum += -logf(p_label) in float64 (+inf for p_label == 0).
+ *   per_class    [K][3] double out: G = the class's foreground count, lo, hi with, in float64 and Fge / Bge (Fgt / Bgt) the
+ *                sums of hist[c][1] / hist[c][0] over the bins >= k (> k),
+ *                  hi = (1/bins) sum_{k=0}^{bins-1} 1 - (G - Fge(k)) / (G + Bge(k)),   lo = the same with Fgt, Bgt.
+ *                lo <= the class's Lovasz extension <= hi and hi - lo <= 1/bins.  lo = hi = 0 when G == 0.
+ *   nll_sum      [1] double out;  counts [3] long long out: good pixels, bad by label, bad by probability.
+ *   workspace    8-byte aligned, at least rmnet_clip_loss_workspace_bytes(K, bins) bytes (0 when K is outside 1 .. 255 or bins
+ *                is no power of two in range).  It begins with hist, uint32 [K][2][bins + 1] (index 0 = background,
+ *                1 = foreground), complete when the call's work is; the per-workgroup partials follow.  The call clears what it
+ *                accumulates into; every output is fully written.  Counts are exact integers and every float64 sum has a fixed
+ *                order: the same bits from call to call.
+ * RMNET_E_INVALID_ARG for a NULL pointer, a non-positive size, K outside 1 .. 255, a bad `bins` or a misaligned pointer;
+ * RMNET_E_UNSUPPORTED for N*H*W >= 2^31; RMNET_E_WORKSPACE for a NULL or short workspace.  Nothing is launched then.
+ * ------------------------------------------------------------------------------------------- */
+size_t rmnet_clip_loss_workspace_bytes(int K, int bins);
+int rmnet_clip_loss_f32(const float *probs, const uint8_t *labels, int N, int K, int H, int W, int ignore_index, int bins,
+                        double *per_class, double *nll_sum, long long *counts, void *workspace, size_t workspace_bytes,
+                        void *stream);
+
 #ifdef __cplusplus
 }
 #endif

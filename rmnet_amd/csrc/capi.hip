@@ -303,4 +303,12 @@ int rmnet_object_edit_softmax_nearest_f32(float* logit, long long logit_batch_st
                                             action, prob, prob_batch_stride, B, K, H, W, static_cast<hipStream_t>(stream));
 }
 
+size_t rmnet_clip_loss_workspace_bytes(int K, int bins) { return clip_loss_ws_bytes(K, bins); }
+
+int rmnet_clip_loss_f32(const float* probs, const uint8_t* labels, int N, int K, int H, int W, int ignore_index, int bins,
+                        double* per_class, double* nll_sum, long long* counts, void* workspace, size_t workspace_bytes, void* stream) {
+  return launch_clip_loss(probs, labels, N, K, H, W, ignore_index, bins, per_class, nll_sum, counts, workspace, workspace_bytes,
+                          static_cast<hipStream_t>(stream));
+}
+
 }  // extern "C"

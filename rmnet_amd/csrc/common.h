@@ -434,6 +434,11 @@ int launch_object_edit_softmax_nearest(float* logit, long long logit_bs, const u
                                        float scale_h, float scale_w, unsigned long long flip_bits, const uint8_t* lut, const uint8_t* action,
                                        float* prob, long long prob_bs, int B, int K, int H, int W, hipStream_t st);
 
+// val_loss.hip: Lovasz-softmax brackets and the NLL sum of a clip from two integer histograms per class
+size_t clip_loss_ws_bytes(int K, int bins);
+int launch_clip_loss(const float* probs, const uint8_t* labels, int N, int K, int H, int W, int ignore_index, int bins, double* per_class,
+                     double* nll_sum, long long* counts, void* ws, size_t ws_bytes, hipStream_t st);
+
 inline int check_launch() { return hipGetLastError() == hipSuccess ? RMNET_OK : RMNET_E_LAUNCH; }
 
 }  // namespace rmnet

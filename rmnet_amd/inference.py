@@ -38,6 +38,21 @@ def segment_video(net, flownet, video, memorize_every=5):
     return est[0].argmax(dim=1).to(torch.uint8)
 
 
+@torch.no_grad()
+def clip_probs(net, flownet, video, memorize_every=5):
+    """``segment_video`` without the argmax: the probabilities float32 [N,K,H,W] of one clip on the model's device, what the
+    validation loss (``losses.validation_loss``) is taken on."""
+    frames = video['frames'].unsqueeze(0)
+    masks = video['masks'].unsqueeze(0)
+    N = frames.shape[1]
+    n_objects = torch.full((1, N), int(video['n_objects']), dtype=torch.long)
+    dev = next(net.parameters()).device
+    frames = frames.to(dev, non_blocking=True)
+    flows = flownet(frames)
+    est = net(frames, masks, flows, n_objects, memorize_every, device=dev)
+    return est[0]
+
+
 # Whether segment_video_tta runs a scale's unflipped and flipped clips as one batch of two.  Measured on an MI355X on 70-frame 480p
 # clips, scales (0.75, 1.0, 1.25) + flip (profiles/r28_a_tta.md): paired 2.51 s against 2.99 s with one object, 5.50 s against 5.83 s with
 # three, the runs of a variant within 0.05 s of each other.
@@ -319,3 +334,40 @@ def evaluate_videos_jf(videos, segment_fn, rank=None, world_size=None):
     f_total = rd.sum_over_ranks(f_total)
     count = max(rd.sum_over_ranks(count), 1.0)
     return {'J-Mean': j_total / count, 'F-Mean': f_total / count, 'JF-Mean': metrics.jf_mean(j_total / count, f_total / count)}
+
+
+def test_videos(videos, probs_fn, rank=None, world_size=None, loss_route=None):
+    """The reference's test driver (core/test.py:69-141) over ``videos`` with ``probs_fn(video) -> float32 [N,K,H,W]`` and ground
+    truth ``video['labels']`` uint8 [N,H,W].  Per clip: the loss of core/test.py:97 (``losses.validation_loss``) over all N
+    frames, frame 0 included; and J and F by the reference's own convention (utils/metrics.py:70-81, 105-116): frame 0 dropped,
+    the last frame kept, objects 1 .. ``video['n_objects']``, the prediction being the argmax of the probabilities.  Across clips
+    as its AverageMeter does: the loss a plain mean over clips, the metrics weighted by the clip's object count, JF-Mean from
+    ``metrics.jf_mean``.  Clips are sharded as in ``evaluate_videos`` and five sums are all-reduced.  Returns {'Loss', 'J-Mean',
+    'F-Mean', 'JF-Mean'} as floats on every rank.  A clip with a label >= K or a probability outside [0, 1] raises RuntimeError;
+    reading that count is the clip's one host synchronisation (the reference's ``loss.item()`` is one too)."""
+    from . import losses
+    if rank is None or world_size is None:
+        rank = torch.distributed.get_rank() if torch.distributed.is_initialized() else 0
+        world_size = torch.distributed.get_world_size() if torch.distributed.is_initialized() else 1
+    mine = rd.my_videos(video_costs(videos), rank, world_size)
+    loss_total, clips, j_total, f_total, weight = 0.0, 0.0, 0.0, 0.0, 0.0
+    for v in mine:
+        probs = probs_fn(videos[v]).contiguous()
+        gt = videos[v]['labels'].to(probs.device).contiguous()
+        n_objects = int(videos[v]['n_objects'])
+        loss = losses.validation_loss(probs, gt, route=loss_route)
+        pred = probs.argmax(dim=1).to(torch.uint8)
+        j = metrics.jaccard_per_object(pred[1:].long(), gt[1:].long(), n_objects)
+        radius = metrics.boundary_radius(pred.shape[-2], pred.shape[-1])
+        f = metrics.f_from_counts(metrics.boundary_counts(pred[1:].contiguous(), gt[1:].contiguous(), n_objects, radius))
+        n_bad = int(loss['n_bad'])                                                           # (the host synchronisation)
+        if n_bad:
+            raise RuntimeError('clip %d: %d pixels have a label >= K or a probability outside [0, 1]' % (v, n_bad))
+        loss_total += float(loss['loss'])
+        clips += 1.0
+        j_total += float(j.mean()) * n_objects
+        f_total += float(f.mean()) * n_objects
+        weight += float(n_objects)
+    loss_total, clips, j_total, f_total, weight = (rd.sum_over_ranks(x) for x in (loss_total, clips, j_total, f_total, weight))
+    j_mean, f_mean = j_total / max(weight, 1.0), f_total / max(weight, 1.0)
+    return {'Loss': loss_total / max(clips, 1.0), 'J-Mean': j_mean, 'F-Mean': f_mean, 'JF-Mean': metrics.jf_mean(j_mean, f_mean)}

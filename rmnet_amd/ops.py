@@ -1327,6 +1327,38 @@ def boundary_match(pred, gt, n_objects, radius):
     return counts
 
 
+def clip_loss(probs, labels, ignore_index=255, bins=1 << 20, want_hist=False):
+    """probs float32 [N,K,H,W] and labels uint8 [N,H,W] on the GPU -> the pieces of the validation loss of core/test.py:97
+    (csrc/val_loss.hip, include/rmnet_hip.h I1), as device tensors and without a sync:
+      'per_class' float64 [K,3]: G (the class's foreground count), lo, hi -- the class's Lovasz extension lies in [lo, hi] and
+                  hi - lo <= 1 / bins; all 0 for a class that no counted pixel has
+      'nll_sum'   float64 0-d: the sum of -logf(p_label) over the counted pixels
+      'counts'    int64 [3]: counted pixels, pixels left out for a label >= K, pixels left out for a probability outside [0, 1]
+      'hist'      with want_hist, int32 [K,2,bins+1]: the integer histograms of the keys (a view of the call's workspace).
+    ``bins`` is a power of two from 2 to 2^22; an ``ignore_index`` outside 0 .. 255 ignores nothing."""
+    _check(probs, 'probs')
+    _check(labels, 'labels', dtype=torch.uint8)
+    if probs.dim() != 4 or labels.dim() != 3 or (probs.shape[0],) + tuple(probs.shape[2:]) != tuple(labels.shape):
+        raise RuntimeError('expected probs [N, K, H, W] and labels [N, H, W]')
+    if labels.device != probs.device:
+        raise RuntimeError('probs and labels must be on the same device')
+    lib = _lib.load()
+    N, K, H, W = probs.shape
+    bins, dev = int(bins), probs.device
+    with torch.cuda.device(dev):
+        per_class = torch.empty(max(K, 1), 3, dtype=torch.float64, device=dev)
+        nll_sum = torch.empty((), dtype=torch.float64, device=dev)
+        counts = torch.empty(3, dtype=torch.int64, device=dev)
+        ws = _ws(lib.rmnet_clip_loss_workspace_bytes(K, bins), dev)
+        rc = lib.rmnet_clip_loss_f32(_ptr(probs), _ptr(labels), N, K, H, W, int(ignore_index), bins, _ptr(per_class), _ptr(nll_sum),
+                                     _ptr(counts), _ptr(ws), ws.numel(), _stream(dev))
+    _lib.check(rc, 'rmnet_clip_loss_f32')
+    out = {'per_class': per_class, 'nll_sum': nll_sum, 'counts': counts}
+    if want_hist:
+        out['hist'] = ws[:K * 2 * (bins + 1) * 4].view(torch.int32).view(K, 2, bins + 1)
+    return out
+
+
 # ------------------------------------------------------------------------------------------------ clip I/O (csrc/clip_io.hip)
 def _three_doubles(v, name):
     v = [float(x) for x in v]
