@@ -159,6 +159,31 @@ int rmnet_memory_read_f32_ev(const float *m_key, const float *m_val, const float
                              int flags, void *workspace, size_t workspace_bytes, void *stream,
                              void *ev_start, void *ev_mid, void *ev_end);
 
+/* Gradients of rmnet_memory_read_f32 (csrc/memory_read_bwd.hip): what loss.backward() sends through MemoryReader.forward
+ * (models/rmnet.py:147-165 with the box masking of :244-248 / :356-358) in the reference's training loop.
+ *   m_key, m_val, q_key, q_val, the sizes, strides and rectangles: the forward's arguments, unchanged.
+ *   mem_val       [no, 2*Do, h, w]  the forward's output (its read-out half enters delta_n = sum_d G[d,n] R[d,n])
+ *   grad_mem_val  [no, 2*Do, h, w]  the gradient that arrives
+ *   d_m_key [no, De, T, h, w], d_m_val [no, Do, T, h, w]  out, addressed by m_key's / m_val's stride rule (a gradient buffer of
+ *                 capacity Tcap is written in its first T frames only; frames >= T are not touched)
+ *   d_q_key [no, De, h, w], d_q_val [no, Do, h, w]        out, contiguous
+ * Any of the four gradient pointers may be NULL: that gradient is not computed, and the others have the same bits as in a
+ * full call.  All four NULL is RMNET_E_INVALID_ARG.  Every element of a requested gradient is written: a cell outside its
+ * rectangle gets 0.  The gradient is that of the EXACT function -- fp32 operands, fp32 accumulate on v_mfma_f32_16x16x4_f32,
+ * P recomputed from per-query (max, sum) statistics -- whatever arithmetic produced mem_val.  No M x N matrix is written:
+ * the workspace is linear in T*h*w + De*h*w + Do.  No atomics: two calls give the same bits.
+ * One code path for De <= 224 (RMNET_E_UNSUPPORTED beyond), any Do, any T, h, w.  Other codes as rmnet_memory_read_f32:
+ * RMNET_E_INVALID_ARG for a NULL input, a non-positive size, a channel stride below T*h*w, one rectangle array without the
+ * other; RMNET_E_WORKSPACE for a NULL or short workspace.  With De > 96 the gradient kernels ask for more than 64 KB of
+ * dynamic LDS: the first call on a device must not come from a stream that is capturing (RMNET_E_UNSUPPORTED). */
+size_t rmnet_memory_read_backward_workspace_bytes(int no, int De, int Do, int T, int h, int w);
+int rmnet_memory_read_backward_f32(const float *m_key, const float *m_val, const float *q_key, const float *q_val,
+                                   int no, int De, int Do, int T, int h, int w,
+                                   long long m_chan_stride, long long m_obj_stride, long long v_chan_stride,
+                                   long long v_obj_stride, const float *mem_val, const float *grad_mem_val,
+                                   const int32_t *mem_rects, const int32_t *qry_rects, float *d_m_key, float *d_m_val,
+                                   float *d_q_key, float *d_q_val, void *workspace, size_t workspace_bytes, void *stream);
+
 /* ---------------------------------------------------------------------------------------------
  * P1/P2 + M1-M3  Regional memory BANK: the form the frame loop uses.
  * Replaces: the K-slot padding, box masking and per-frame torch.cat of the whole memory

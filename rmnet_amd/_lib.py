@@ -38,6 +38,12 @@ SIGNATURES = {
         ctypes.c_int, ctypes.c_int, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_longlong,
         ctypes.c_longlong, c_f32p, c_f32p, c_i32p, c_i32p, ctypes.c_int, ctypes.c_void_p,
         ctypes.c_size_t, ctypes.c_void_p]),
+    'rmnet_memory_read_backward_workspace_bytes': (ctypes.c_size_t, [ctypes.c_int] * 6),
+    'rmnet_memory_read_backward_f32': (ctypes.c_int, [
+        c_f32p, c_f32p, c_f32p, c_f32p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+        ctypes.c_int, ctypes.c_int, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_longlong,
+        ctypes.c_longlong, c_f32p, c_f32p, c_i32p, c_i32p, c_f32p, c_f32p, c_f32p, c_f32p, ctypes.c_void_p,
+        ctypes.c_size_t, ctypes.c_void_p]),
     'rmnet_memory_read_f32_ev': (ctypes.c_int, [
         c_f32p, c_f32p, c_f32p, c_f32p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
         ctypes.c_int, ctypes.c_int, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_longlong,

@@ -78,6 +78,28 @@ int rmnet_memory_read_f32(const float* m_key, const float* m_val, const float* q
                                   nullptr, nullptr, nullptr);
 }
 
+size_t rmnet_memory_read_backward_workspace_bytes(int no, int De, int Do, int T, int h, int w) {
+  if (no <= 0 || De <= 0 || Do <= 0 || T <= 0 || h <= 0 || w <= 0) return 0;
+  return memory_read_bwd_ws_bytes(no, De, Do, T, h, w);
+}
+
+int rmnet_memory_read_backward_f32(const float* m_key, const float* m_val, const float* q_key, const float* q_val, int no, int De,
+                                   int Do, int T, int h, int w, long long m_chan_stride, long long m_obj_stride,
+                                   long long v_chan_stride, long long v_obj_stride, const float* mem_val,
+                                   const float* grad_mem_val, const int32_t* mem_rects, const int32_t* qry_rects, float* d_m_key,
+                                   float* d_m_val, float* d_q_key, float* d_q_val, void* workspace, size_t workspace_bytes,
+                                   void* stream) {
+  MemReadBwdArgs a;
+  a.mk = m_key; a.mv = m_val; a.qk = q_key; a.qv = q_val;
+  a.out = mem_val; a.gout = grad_mem_val;
+  a.mem_rects = mem_rects; a.qry_rects = qry_rects;
+  a.dmk = d_m_key; a.dmv = d_m_val; a.dqk = d_q_key; a.dqv = d_q_val;
+  a.no = no; a.De = De; a.Do = Do; a.T = T; a.h = h; a.w = w;
+  a.mk_cs = m_chan_stride; a.mk_os = m_obj_stride; a.mv_cs = v_chan_stride; a.mv_os = v_obj_stride;
+  a.ws = workspace; a.ws_bytes = workspace_bytes;
+  return launch_memory_read_bwd(a, static_cast<hipStream_t>(stream));
+}
+
 size_t rmnet_bank_bytes(int no, int Tcap, int h, int w) {
   if (no <= 0 || Tcap <= 0 || h <= 0 || w <= 0) return 0;
   return bank_bytes(no, Tcap, h, w);

@@ -158,6 +158,21 @@ struct MemReadArgs {
 size_t memory_read_ws_bytes(int no, int De, int Do, int T, int h, int w, int flags);
 int launch_memory_read(const MemReadArgs& a, hipStream_t st);
 
+// memory_read_bwd.hip: the gradients of the read (any pointer of dmk / dmv / dqk / dqv may be null)
+struct MemReadBwdArgs {
+  const float *mk, *mv, *qk, *qv;
+  const float *out, *gout;       // the forward's mem_val and its gradient, [no][2 Do][h w]
+  const int32_t* mem_rects;
+  const int32_t* qry_rects;
+  float *dmk, *dmv, *dqk, *dqv;
+  int no, De, Do, T, h, w;
+  long long mk_cs, mk_os, mv_cs, mv_os;
+  void* ws;
+  size_t ws_bytes;
+};
+size_t memory_read_bwd_ws_bytes(int no, int De, int Do, int T, int h, int w);
+int launch_memory_read_bwd(const MemReadBwdArgs& a, hipStream_t st);
+
 // ---- split-fp16 memory bank (bank.hip) -------------------------------------------------------
 struct BankView {
   char *kh, *kl;   // [no][Tcap][hwp][128] fp16 hi / lo  (cell-major keys)

@@ -135,15 +135,8 @@ def boxes_to_cell_rects(bboxes, pad_l, pad_t, stride, cells_h, cells_w, k_per_ba
     return out
 
 
-def memory_read(m_key, m_val, q_key, q_val, mem_rects=None, qry_rects=None, want_p=False, flags=0,
-                T=None, out=None, events=None):
-    """Fused (regional) memory read.
-
-    m_key [no,De,Tcap,h,w], m_val [no,Do,Tcap,h,w] (only the first ``T`` frames are read; default
-    all), q_key [no,De,h,w], q_val [no,Do,h,w]; optional mem_rects [no,T,4] / qry_rects [no,4] i32.
-    ``events`` = (ev_start, ev_mid, ev_end) raw hipEvent_t handles (ints) recorded around the two
-    kernels of the fast path (profiling only).
-    Returns (mem_val [no,2*Do,h,w], p [no,T*h*w,h*w] | None)."""
+def _check_read_args(m_key, m_val, q_key, q_val, mem_rects, qry_rects, T):
+    """The argument rules shared by memory_read and memory_read_backward; returns (no, De, Do, Tcap, T, h, w)."""
     for t, n in ((m_key, 'm_key'), (m_val, 'm_val'), (q_key, 'q_key'), (q_val, 'q_val')):
         _check(t, n)
     if m_key.dim() != 5 or m_val.dim() != 5 or q_key.dim() != 4 or q_val.dim() != 4:
@@ -163,6 +156,88 @@ def memory_read(m_key, m_val, q_key, q_val, mem_rects=None, qry_rects=None, want
         _check(qry_rects, 'qry_rects', torch.int32)
         if mem_rects.numel() != no * T * 4 or qry_rects.numel() != no * 4:
             raise RuntimeError('mem_rects must be [no,T,4] and qry_rects [no,4]')
+    return no, De, Do, Tcap, T, h, w
+
+
+def memory_read_backward(m_key, m_val, q_key, q_val, mem_val, grad_mem_val, mem_rects=None, qry_rects=None, T=None,
+                         need=(True, True, True, True)):
+    """Gradients of ``memory_read`` (csrc/memory_read_bwd.hip): fp32 MFMA kernels that recompute the soft-max from per-query
+    statistics, so the result is the gradient of the exact function whatever arithmetic produced ``mem_val``.
+
+    The first four arguments, the rectangles and ``T`` are the forward's; ``mem_val`` is its output and ``grad_mem_val`` the
+    gradient that arrives, both [no,2*Do,h,w].  ``need`` = which of (d m_key, d m_val, d q_key, d q_val) to compute; the others
+    come back as None.  With fewer frames read than the memory holds (T < Tcap) the frames beyond T get a zero gradient.
+    Deterministic: no atomics, equal bits from call to call."""
+    no, De, Do, Tcap, T, h, w = _check_read_args(m_key, m_val, q_key, q_val, mem_rects, qry_rects, T)
+    for t, n in ((mem_val, 'mem_val'), (grad_mem_val, 'grad_mem_val')):
+        _check(t, n)
+        if tuple(t.shape) != (no, 2 * Do, h, w):
+            raise RuntimeError('%s must be [no, 2*Do, h, w]' % n)
+    need = tuple(bool(x) for x in need)
+    if len(need) != 4 or not any(need):
+        raise RuntimeError('need must name at least one of the four gradients')
+    lib = _lib.load()
+    dev = m_key.device
+    with torch.cuda.device(dev):
+        new = torch.empty_like if T == Tcap else torch.zeros_like       # (frames >= T are not written by the kernels)
+        d_mk = new(m_key) if need[0] else None
+        d_mv = new(m_val) if need[1] else None
+        d_qk = torch.empty_like(q_key) if need[2] else None
+        d_qv = torch.empty_like(q_val) if need[3] else None
+        ws = _ws(lib.rmnet_memory_read_backward_workspace_bytes(no, De, Do, T, h, w), dev)
+        cs = Tcap * h * w
+        rc = lib.rmnet_memory_read_backward_f32(_ptr(m_key), _ptr(m_val), _ptr(q_key), _ptr(q_val), no, De, Do, T, h, w,
+                                                cs, cs * De, cs, cs * Do, _ptr(mem_val), _ptr(grad_mem_val), _ptr(mem_rects),
+                                                _ptr(qry_rects), _ptr(d_mk), _ptr(d_mv), _ptr(d_qk), _ptr(d_qv), _ptr(ws), ws.numel(),
+                                                _stream(dev))
+    _lib.check(rc, 'rmnet_memory_read_backward_f32')
+    return d_mk, d_mv, d_qk, d_qv
+
+
+class _MemoryReadFn(torch.autograd.Function):
+    """memory_read under autograd: the forward is the call every other caller makes, the backward is memory_read_backward."""
+
+    @staticmethod
+    def forward(ctx, m_key, m_val, q_key, q_val, mem_rects, qry_rects, want_p, flags, T, events):
+        mem_val, p = memory_read(m_key.detach(), m_val.detach(), q_key.detach(), q_val.detach(), mem_rects, qry_rects, want_p, flags, T,
+                                 None, events)
+        ctx.save_for_backward(m_key, m_val, q_key, q_val, mem_val)
+        ctx.rects = (mem_rects, qry_rects)
+        ctx.T = T
+        if p is None:
+            return mem_val, None
+        ctx.mark_non_differentiable(p)
+        return mem_val, p
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_mem_val, _grad_p):
+        m_key, m_val, q_key, q_val, mem_val = ctx.saved_tensors
+        grads = memory_read_backward(m_key, m_val, q_key, q_val, mem_val, grad_mem_val.contiguous(), ctx.rects[0], ctx.rects[1], ctx.T,
+                                     need=ctx.needs_input_grad[:4])
+        return grads + (None,) * 6
+
+
+def memory_read(m_key, m_val, q_key, q_val, mem_rects=None, qry_rects=None, want_p=False, flags=0,
+                T=None, out=None, events=None):
+    """Fused (regional) memory read.
+
+    m_key [no,De,Tcap,h,w], m_val [no,Do,Tcap,h,w] (only the first ``T`` frames are read; default
+    all), q_key [no,De,h,w], q_val [no,Do,h,w]; optional mem_rects [no,T,4] / qry_rects [no,4] i32.
+    ``events`` = (ev_start, ev_mid, ev_end) raw hipEvent_t handles (ints) recorded around the two
+    kernels of the fast path (profiling only).
+    Returns (mem_val [no,2*Do,h,w], p [no,T*h*w,h*w] | None).
+
+    Differentiable in its four float inputs: when grad mode is on and one of them requires grad, the call is recorded as one
+    ``torch.autograd.Function`` whose backward is ``memory_read_backward`` -- the gradient of the exact function, whatever
+    ``flags`` the forward ran with.  ``p`` is not differentiable, there is no double backward, and ``out=`` cannot be combined
+    with a gradient.  Every other call takes the plain path."""
+    if torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad for t in (m_key, m_val, q_key, q_val)):
+        if out is not None:
+            raise RuntimeError('memory_read: out= cannot be used when a gradient is needed')
+        _check_read_args(m_key, m_val, q_key, q_val, mem_rects, qry_rects, T)
+        return _MemoryReadFn.apply(m_key, m_val, q_key, q_val, mem_rects, qry_rects, want_p, flags, T, events)
+    no, De, Do, Tcap, T, h, w = _check_read_args(m_key, m_val, q_key, q_val, mem_rects, qry_rects, T)
     lib = _lib.load()
     dev = m_key.device
     with torch.cuda.device(dev):

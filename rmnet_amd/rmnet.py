@@ -44,7 +44,13 @@ class MemoryReader(nn.Module):
 
     ``p`` (the [no, THW, HW] affinity the reference returns as ``viz`` and never uses, :361-366) is
     only computed when ``return_affinity=True``; otherwise the second element is ``None``.
-    Optional ``mem_rects`` / ``qry_rects`` select the fused regional form."""
+    Optional ``mem_rects`` / ``qry_rects`` select the fused regional form.
+
+    Differentiable, in training mode too and with any ``precision``: when an input requires grad, ``mem_val`` carries a
+    ``grad_fn`` and ``backward()`` runs the fp32 MFMA kernels of csrc/memory_read_bwd.hip (``ops.memory_read_backward``).  The
+    gradient is that of the EXACT function -- soft-max recomputed in fp32 from per-query statistics -- whatever arithmetic the
+    forward ran in, so 'f16' and 'qx' forwards get fp32-class gradients of the function they approximate.  ``p`` is not
+    differentiable and there is no double backward.  (``RMNet`` itself stays inference-only.)"""
 
     def __init__(self, return_affinity=False, precision='split'):
         super().__init__()
