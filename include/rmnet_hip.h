@@ -396,6 +396,25 @@ int rmnet_conv_split_pre_f32(const void *x, const void *wpack, const float *w_un
                              int32_t *range_word, void *stream);
 int rmnet_split_act_f32(const float *x, long long M, int C, int relu, void *out, int32_t *range_word, void *stream);
 
+/* The key / value heads of the frame step on the cells that the regional memory uses (additive export, same ABI version;
+ * csrc/conv_split.hip: conv_split_region, the RG instance of the kernel's body).  The convolution of rmnet_conv_split_pre_f32 with
+ * RMNET_CONV_X_SPLIT and two outputs, computed only for the cells inside one rectangle per image:
+ *   rects [N][4] int32 (cx0, cx1, cy0, cy1), inclusive, on the device; clamped to the map exactly as the bank kernels clamp theirs
+ *         (max(., 0), min(., W - 1 / H - 1)); cx1 < cx0 or cy1 < cy0 after that: an empty rectangle;
+ *   out   [N, out_split, H, W] and out2 [N, Cout - out_split, H, W] fp32, NCHW (the layout rmnet_bank_append_f32_at and
+ *         rmnet_bank_read_f32_at take).  A cell inside its image's rectangle holds the bits that rmnet_conv_split_pre_f32 gives it;
+ *         every other cell is +0.0, written by this kernel: the outputs need no initialisation.
+ * The GEMM's rows are the cells of all rectangles, image after image, each rectangle row-major; the tile is the 128 x 128 one, the K
+ * order and the epilogue's arithmetic are those of the dense kernel.  The grid is the worst case, ceil(N*H*W / 128) x Cout / 128:
+ * nothing is read back, and a workgroup past the last row only writes its share of the zeros.  x is in split form, so nothing is
+ * added to the range word.
+ * Rules: those of rmnet_conv_split_pre_f32, and RMNET_E_INVALID_ARG for rects == NULL or not 16-byte aligned, a flag other than
+ * RMNET_CONV_X_SPLIT (required) and RMNET_CONV_RELU_OUT, out2 == NULL, or an output that overlaps rects; RMNET_E_UNSUPPORTED for
+ * ksize != 3, stride != 1, Cout % 128 != 0 or N > 64 (the caller then runs the dense head). */
+int rmnet_conv_split_region_f32(const void *x, const void *wpack, const float *w_unscale, const float *shift, int flags, int N, int H,
+                                int W, int Cin, int Cout, int ksize, int stride, const int32_t *rects, float *out, float *out2,
+                                int out_split, int32_t *range_word, void *stream);
+
 /* The trunks' stride-1 3x3 bottleneck convolutions on the kernel that stages a whole tap row of activations in LDS once (additive
  * export, same ABI version; csrc/conv_rows.hip: conv_rows<C>): the arguments and argument rules of rmnet_conv_split_pre_f32, and its
  * results bit for bit, range word included -- the K order per accumulator, the operand bits and the epilogue are the same -- for

@@ -106,6 +106,9 @@ SIGNATURES = {
     'rmnet_conv_rows_pre_f32': (ctypes.c_int, [
         ctypes.c_void_p, ctypes.c_void_p, c_f32p, c_f32p, c_f32p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
         ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, c_f32p, ctypes.c_int, c_i32p, ctypes.c_void_p]),
+    'rmnet_conv_split_region_f32': (ctypes.c_int, [
+        ctypes.c_void_p, ctypes.c_void_p, c_f32p, c_f32p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+        ctypes.c_int, ctypes.c_int, ctypes.c_int, c_i32p, c_f32p, c_f32p, ctypes.c_int, c_i32p, ctypes.c_void_p]),
     'rmnet_split_act_f32': (ctypes.c_int, [
         c_f32p, ctypes.c_longlong, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, c_i32p, ctypes.c_void_p]),
     'rmnet_stem_split_f32': (ctypes.c_int, [

@@ -38,6 +38,14 @@
 //   the store          OS 0: a lane's 4 channels as one float4, to out, or to out / out2 on either side of csplit;
 //                      OS 1: as 8 bytes of hi and 8 bytes of lo (split4), the elements outside the window counted here, once each.
 // 12 instances: 3 tiles x 4 pairs.  rmnet_conv_split_f32 is the (0, 0) pair alone, rmnet_conv_split_pre_f32 takes all four.
+//
+// The code of all of them is conv_split_body<..., RG>; the kernel conv_split<...> calls it with RG = false.  RG = true is the REGIONAL
+// instance, the kernel conv_split_region (rmnet_conv_split_region_f32): the Mid tile with split input and two fp32 outputs, for the
+// key / value heads of the frame step, whose consumers (csrc/bank.hip: bk_append, bk_main) use only the cells inside one rectangle
+// per image.  Its GEMM rows are those cells, compacted -- image after image, each rectangle row-major -- through a prefix table in
+// LDS; its outputs are NCHW, and every cell outside a rectangle is written as +0.0 by the workgroup that owns the cell's place in the
+// flat N*H*W index.  The weight path, the mma, the K order and the epilogue's arithmetic are the dense kernel's, so a cell inside a
+// rectangle gets the dense kernel's bits (tests/test_conv_split_region.py).  64 KB + 1284 B of LDS, 126 VGPRs: two workgroups per CU.
 #include "split_f16.h"      // the vector types, kKT, kThreads, the activation scale, swz, split4, overlap
 
 namespace rmnet {
@@ -57,10 +65,43 @@ struct SplitArgs {
   int M, H, W, Ho, Wo, Cin, Cout, csplit, ksize, stride, pad, relu_in, relu_out;
 };
 
-// WPE: waves per SIMD the register allocation must allow -- 2 (one workgroup per CU) for Big, 4 (two) for Mid / Narrow
-template <int WM, int WN, int TI, int TJ, int WPE, bool XS, bool OS>
-__global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(WPE))) void conv_split(SplitArgs a) {
+// The regional instance (RG; the kernel conv_split_region below): M = N*H*W cells, out / out2 are NCHW
+struct RegionArgs : SplitArgs {
+  const int32_t* rects;    // [N][4] (cx0, cx1, cy0, cy1), inclusive; the kernel clamps them to the map as bk_append / bk_main do
+};
+constexpr int kRegionMaxObjects = 64;      // objects per launch: the size of the LDS tables (as kBankMaxObj, a launch of the bank read)
+
+// The regional instance's row map, in LDS next to the double buffer: pref[o] = cells inside the rectangles of the objects before o
+// (pref[N] = the GEMM's rows), rect[o] = object o's clamped rectangle.  Row g is cell g - pref[o] of object o in bk_append's
+// enumeration (the rectangle row-major): cy0 + n / rw, cx0 + n % rw.
+struct RegionTables {
+  int pref[kRegionMaxObjects + 1];
+  int rect[kRegionMaxObjects][4];
+};
+__device__ __forceinline__ RegionTables& region_tables() {
+  __shared__ RegionTables t;
+  return t;
+}
+// g < pref[NO]: the object and the cell (row, column) of row g.  An empty object has no row: pref[o] <= g < pref[o + 1] names one
+__device__ __forceinline__ void region_row(const RegionTables& t, int NO, int g, int& o, int& cy, int& cx) {
+  int lo = 0, hi = NO;                  // pref[lo] <= g < pref[hi]
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if (t.pref[mid] <= g) lo = mid; else hi = mid;
+  }
+  const int n = g - t.pref[lo], rw = t.rect[lo][1] - t.rect[lo][0] + 1, ry = n / rw;
+  o = lo;
+  cy = t.rect[lo][2] + ry;
+  cx = t.rect[lo][0] + (n - ry * rw);
+}
+
+// The body of every instance.  WPE: waves per SIMD the register allocation must allow -- 2 (one workgroup per CU) for Big, 4 (two)
+// for Mid / Narrow.  RG: the GEMM's rows are the cells inside the objects' rectangles, compacted; what differs stands in
+// `if constexpr (RG)` branches (the row map of the loader and of the epilogue, the NCHW stores, the zero fill).
+template <int WM, int WN, int TI, int TJ, int WPE, bool XS, bool OS, bool RG, class Args>
+__device__ __forceinline__ void conv_split_body(const Args a) {
   static_assert(WM * WN * 64 == kThreads, "8 waves");
+  static_assert(!RG || (XS && !OS), "the regional instance takes a split input and writes fp32");
   constexpr int MT = WM * TI * 16, NT = WN * TJ * 16;
   constexpr int XI = MT / 64;                      // activation items per thread and step (16 bytes each, either form)
   constexpr int WI = NT / 64;                      // weight 16-byte chunks per thread and step
@@ -78,14 +119,68 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(WPE)))
   // loader items: activations XI x 16 bytes (pixel p = tid/8 + 64i; c4: see load_x / store_x in the header), weights WI x 16 B
   const int c4 = tid & 7;
   int pbase[XI], ph[XI], pw[XI];      // input pixel of tap (0, 0): flat index, row, column (outside the map: not read)
+  if constexpr (RG) {
+    // One wave clamps the rectangles and scans their areas into the tables
+    RegionTables& rt = region_tables();
+    const int NO = a.M / HWo;
+    if (tid < RMNET_WAVE) {
+      Rect rc{1, 0, 1, 0};
+      if (tid < NO) {
+        const int32_t* r = a.rects + 4 * tid;
+        rc = Rect{max(r[0], 0), min(r[1], a.W - 1), max(r[2], 0), min(r[3], a.H - 1)};
+      }
+      const int incl = wave_scan_incl_fast(rc.area());
+      if (tid == 0) rt.pref[0] = 0;
+      if (tid < NO) {
+        rt.pref[tid + 1] = incl;
+        rt.rect[tid][0] = rc.cx0; rt.rect[tid][1] = rc.cx1; rt.rect[tid][2] = rc.cy0; rt.rect[tid][3] = rc.cy1;
+      }
+    }
+    __syncthreads();
+    // The fill: the cells [m0, m0 + MT) of the flat N*H*W index that lie outside their object's rectangle are +0.0 in this
+    // workgroup's NT channels.  The grid covers every cell and no workgroup computes a cell outside a rectangle, so every element
+    // of the outputs is written exactly once.  Thread = one cell (a wave stores 64 consecutive floats of a channel plane) and the
+    // channels tid / MT, + kThreads / MT, ...
+    {
+      static_assert(kThreads % MT == 0, "a thread of the fill owns one cell");
+      const int f = m0 + tid % MT;
+      bool fill = f < a.M;
+      const int o = fill ? f / HWo : 0, cell = f - o * HWo;
+      if (fill) {
+        const int cy = cell / a.Wo, cx = cell - cy * a.Wo;
+        fill = !Rect{rt.rect[o][0], rt.rect[o][1], rt.rect[o][2], rt.rect[o][3]}.contains(cy, cx);
+      }
+      if (fill) {
+        const int c2 = a.Cout - a.csplit;
+        for (int c = n0 + tid / MT; c < n0 + NT; c += kThreads / MT) {
+          if (c < a.csplit)
+            a.out[((size_t)o * a.csplit + c) * HWo + cell] = 0.0f;
+          else
+            a.out2[((size_t)o * c2 + (c - a.csplit)) * HWo + cell] = 0.0f;
+        }
+      }
+    }
+    const int total = rt.pref[NO];
+    if (m0 >= total) return;            // (the whole workgroup: no row of this tile is a cell of a rectangle)
 #pragma unroll
-  for (int i = 0; i < XI; ++i) {
-    const int m = m0 + (tid >> 3) + 64 * i;
-    const int n = m / HWo, r = m - n * HWo;
-    const int ho = r / a.Wo, wo = r - ho * a.Wo;
-    ph[i] = m < a.M ? ho * a.stride - a.pad : -4;       // (past M: every tap's row is < 0)
-    pw[i] = wo * a.stride - a.pad;
-    pbase[i] = (n * a.H + ph[i]) * a.W + pw[i];
+    for (int i = 0; i < XI; ++i) {
+      const int g = m0 + (tid >> 3) + 64 * i;
+      int o = 0, cy = -4 + a.pad, cx = a.pad;       // (past the last row: every tap's row is < 0)
+      if (g < total) region_row(rt, NO, g, o, cy, cx);
+      ph[i] = cy - a.pad;
+      pw[i] = cx - a.pad;
+      pbase[i] = (o * a.H + ph[i]) * a.W + pw[i];
+    }
+  } else {
+#pragma unroll
+    for (int i = 0; i < XI; ++i) {
+      const int m = m0 + (tid >> 3) + 64 * i;
+      const int n = m / HWo, r = m - n * HWo;
+      const int ho = r / a.Wo, wo = r - ho * a.Wo;
+      ph[i] = m < a.M ? ho * a.stride - a.pad : -4;       // (past M: every tap's row is < 0)
+      pw[i] = wo * a.stride - a.pad;
+      pbase[i] = (n * a.H + ph[i]) * a.W + pw[i];
+    }
   }
   f32x4 xr[XI];
   u32x4 xq[XI];
@@ -266,7 +361,7 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(WPE)))
   // dependent ones; the loader's registers are dead by now).  This is safe with out == res: a thread reads exactly the elements it
   // later writes, and no other thread touches them.
   f32x4 r[TI][TJ];
-  if (a.res) {
+  if (!RG && a.res) {
 #pragma unroll
     for (int i = 0; i < TI; ++i) {
       const int m = m0 + wm * TI * 16 + i * 16 + fr;
@@ -293,6 +388,41 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(WPE)))
   for (int j = 0; j < TJ; ++j)
 #pragma unroll
     for (int i = 0; i < TI; ++i) asm volatile("" : "+v"(acc[i][j]));
+  if constexpr (RG) {
+    // NCHW: a lane's 4 channels are 4 dword stores, the 16 lanes of a tile's pixels cover 16 consecutive rows of the map (cells
+    // that are consecutive in memory, but for the ends of the rectangle's rows).  No residual; rows past the last are not stored.
+    const RegionTables& rt = region_tables();
+    const int NO = a.M / HWo, total = rt.pref[NO];
+    int po[TI], pcell[TI];
+#pragma unroll
+    for (int i = 0; i < TI; ++i) {
+      const int g = m0 + wm * TI * 16 + i * 16 + fr;
+      int cy = 0, cx = 0;
+      po[i] = -1;
+      if (g < total) region_row(rt, NO, g, po[i], cy, cx);
+      pcell[i] = cy * a.Wo + cx;
+    }
+    const int c2 = a.Cout - a.csplit;
+#pragma unroll
+    for (int j = 0; j < TJ; ++j) {
+      const int co = n0 + wn * TJ * 16 + j * 16 + 4 * fc;
+      const bool key = co < a.csplit;        // (csplit % 4 == 0: a lane's 4 channels fall on one side)
+#pragma unroll
+      for (int i = 0; i < TI; ++i) {
+        if (po[i] < 0) continue;
+        f32x4 v = acc[i][j];
+        if (a.relu_out) {
+#pragma unroll
+          for (int e = 0; e < 4; ++e) v[e] = v[e] < 0.0f ? 0.0f : v[e];
+        }
+        float* o = key ? a.out + ((size_t)po[i] * a.csplit + co) * HWo + pcell[i]
+                       : a.out2 + ((size_t)po[i] * c2 + (co - a.csplit)) * HWo + pcell[i];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) o[(size_t)e * HWo] = v[e];
+      }
+    }
+    return;
+  }
 #pragma unroll
   for (int j = 0; j < TJ; ++j) {
     const int co = n0 + wn * TJ * 16 + j * 16 + 4 * fc;
@@ -324,6 +454,16 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(WPE)))
     }
   }
   if (a.range && bad) atomicAdd(a.range, bad);
+}
+
+template <int WM, int WN, int TI, int TJ, int WPE, bool XS, bool OS>
+__global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(WPE))) void conv_split(SplitArgs a) {
+  conv_split_body<WM, WN, TI, TJ, WPE, XS, OS, false>(a);
+}
+
+// The regional instance: the Mid tile, split in, fp32 NCHW out (the key / value heads of the frame step; see the entry below)
+__global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(4))) void conv_split_region(RegionArgs a) {
+  conv_split_body<2, 4, 4, 2, 4, true, false, true>(a);
 }
 
 template <int WM, int WN, int TI, int TJ, int WPE, bool XS, bool OS>
@@ -374,16 +514,19 @@ __global__ __launch_bounds__(kSplitActThreads) void split_act(const float* __res
   if (range && bad) atomicAdd(range, bad);
 }
 
-// The argument rules and the launch of both entries.  `allowed`: the flag bits the entry takes.  Everything that is an invalid
-// argument is decided before anything that is unsupported, except the overlaps, which need the sizes.
+// The argument rules and the launch of the three entries.  `allowed`: the flag bits the entry takes.  Everything that is an invalid
+// argument is decided before anything that is unsupported, except the overlaps, which need the sizes.  `region`: the regional
+// entry, whose own rules stand next to the shared ones of their kind: `rects`, a split input and two fp32 outputs (invalid
+// otherwise); 3x3, stride 1, Cout % 128 == 0 and at most kRegionMaxObjects images (unsupported otherwise); no output on `rects`.
 int conv_split_entry(const void* x, const void* wpack, const float* w_unscale, const float* shift, const float* res, int flags, int allowed,
                      int N, int H, int W, int Cin, int Cout, int ksize, int stride, void* out, float* out2, int out_split,
-                     int32_t* range_word, void* stream) {
+                     int32_t* range_word, void* stream, bool region = false, const int32_t* rects = nullptr) {
   if (!x || !wpack || !w_unscale || !out || N <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0) return RMNET_E_INVALID_ARG;
   if (flags & ~allowed) return RMNET_E_INVALID_ARG;
   const bool xs = (flags & RMNET_CONV_X_SPLIT) != 0, os = (flags & RMNET_CONV_OUT_SPLIT) != 0;
   if (xs && (flags & RMNET_CONV_RELU_IN)) return RMNET_E_INVALID_ARG;      // (the producer of a split tensor applies it)
   if (os && out2) return RMNET_E_INVALID_ARG;
+  if (region && (!rects || !xs || !out2 || (reinterpret_cast<uintptr_t>(rects) & 15))) return RMNET_E_INVALID_ARG;
   if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(wpack) | reinterpret_cast<uintptr_t>(w_unscale) |
        reinterpret_cast<uintptr_t>(shift) | reinterpret_cast<uintptr_t>(res) | reinterpret_cast<uintptr_t>(out) |
        reinterpret_cast<uintptr_t>(out2)) & 15)
@@ -391,6 +534,7 @@ int conv_split_entry(const void* x, const void* wpack, const float* w_unscale, c
   if (out2 && (res || out_split <= 0 || out_split >= Cout || out_split % 4)) return RMNET_E_INVALID_ARG;
   if ((ksize != 1 && ksize != 3) || (stride != 1 && stride != 2)) return RMNET_E_UNSUPPORTED;
   if (Cin % kKT || Cout % 64) return RMNET_E_UNSUPPORTED;
+  if (region && (ksize != 3 || stride != 1 || Cout % 128 || N > kRegionMaxObjects)) return RMNET_E_UNSUPPORTED;
   const int pad = ksize / 2;
   const int Ho = (H + 2 * pad - ksize) / stride + 1, Wo = (W + 2 * pad - ksize) / stride + 1;
   const long long Mi = (long long)N * H * W, M = (long long)N * Ho * Wo;
@@ -405,7 +549,9 @@ int conv_split_entry(const void* x, const void* wpack, const float* w_unscale, c
   if (out2) {
     if (overlap(out2, M * (Cout - c1) * 4, x, xbytes) || overlap(out2, M * (Cout - c1) * 4, out, M * c1 * 4)) return RMNET_E_INVALID_ARG;
   }
-  SplitArgs a;
+  if (region && (overlap(out, M * c1 * 4, rects, 16LL * N) || overlap(out2, M * (Cout - c1) * 4, rects, 16LL * N))) return RMNET_E_INVALID_ARG;
+  RegionArgs a;
+  a.rects = rects;
   a.x = xs ? nullptr : reinterpret_cast<const float*>(x);
   a.xs = xs ? reinterpret_cast<const _Float16*>(x) : nullptr;
   a.wp = reinterpret_cast<const u32x4*>(wpack); a.unscale = w_unscale; a.shift = shift; a.res = res;
@@ -415,7 +561,9 @@ int conv_split_entry(const void* x, const void* wpack, const float* w_unscale, c
   a.relu_in = (flags & RMNET_CONV_RELU_IN) != 0;
   a.relu_out = (flags & RMNET_CONV_RELU_OUT) != 0;
   hipStream_t st = (hipStream_t)stream;
-  if (xs && os) launch_tile<true, true>(a, st);
+  if (region)       // the grid of the worst case, every cell inside its rectangle: the rectangles stay on the device
+    hipLaunchKernelGGL(conv_split_region, dim3((unsigned)((a.M + 127) / 128), (unsigned)(a.Cout / 128)), dim3(kThreads), 0, st, a);
+  else if (xs && os) launch_tile<true, true>(a, st);
   else if (xs) launch_tile<true, false>(a, st);
   else if (os) launch_tile<false, true>(a, st);
   else launch_tile<false, false>(a, st);
@@ -438,6 +586,13 @@ extern "C" int rmnet_conv_split_pre_f32(const void* x, const void* wpack, const 
   return rmnet::conv_split_entry(x, wpack, w_unscale, shift, res, flags,
                                  RMNET_CONV_RELU_IN | RMNET_CONV_RELU_OUT | RMNET_CONV_X_SPLIT | RMNET_CONV_OUT_SPLIT, N, H, W, Cin, Cout,
                                  ksize, stride, out, out2, out_split, range_word, stream);
+}
+
+extern "C" int rmnet_conv_split_region_f32(const void* x, const void* wpack, const float* w_unscale, const float* shift, int flags, int N,
+                                           int H, int W, int Cin, int Cout, int ksize, int stride, const int32_t* rects, float* out,
+                                           float* out2, int out_split, int32_t* range_word, void* stream) {
+  return rmnet::conv_split_entry(x, wpack, w_unscale, shift, nullptr, flags, RMNET_CONV_RELU_OUT | RMNET_CONV_X_SPLIT, N, H, W, Cin, Cout,
+                                 ksize, stride, out, out2, out_split, range_word, stream, true, rects);
 }
 
 extern "C" int rmnet_split_act_f32(const float* x, long long M, int C, int relu, void* out, int32_t* range_word, void* stream) {

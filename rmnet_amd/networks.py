@@ -393,7 +393,11 @@ class KeyValue(nn.Module):
         self.key_conv = nn.Conv2d(indim, keydim, 3, padding=1)
         self.value_conv = nn.Conv2d(indim, valdim, 3, padding=1)
 
-    def forward(self, x):
+    def forward(self, x, rects=None):
+        """(key, value), channels-last.  ``rects`` (int32 [N, 4] on the device, one cell rectangle per image): on the split-fp16 path
+        with pre-split activations the heads are computed only inside the rectangles (``ops.conv_split(..., rects=)``) and come back
+        NCHW-contiguous, +0.0 outside; on every other path, and for more images than the kernel's tables hold, ``rects`` is not
+        looked at and the call is the one without it."""
         if _split_path_ok(self, x, self.key_conv, ('full', 'split', 'trunk')):
             # both heads in ONE launch of the split-fp16 kernel over the concatenated [key | value] pack, written as two tensors
             from . import ops
@@ -402,6 +406,9 @@ class KeyValue(nn.Module):
             if conv_presplit():
                 # r4 comes from another kernel: one pass splits it (and counts), instead of 9 taps x 5 Cout tiles doing so
                 x = ops.split_act(x, range_word=rw)
+                if rects is not None and x.shape[0] <= ops.KV_REGION_MAX_OBJECTS:
+                    return ops.conv_split(x, self._wp, self._wu, self._bkv, ksize=3, range_word=rw, split=self.key_conv.out_channels,
+                                          rects=rects)
             return ops.conv_split(x, self._wp, self._wu, self._bkv, ksize=3, range_word=rw, split=self.key_conv.out_channels)
         return self.key_conv(x), self.value_conv(x)
 

@@ -834,8 +834,26 @@ def trunk_rows_enabled():
     return v.strip() == '1'
 
 
+# The key / value heads of ``RMNet.frame_step`` on the regional kernel (csrc/conv_split.hip: conv_split_region -- only the cells
+# inside the boxes are computed, the outputs are NCHW; the same bits inside the boxes) when RMNET_KV_REGION is not set.  The rule:
+# True only if every bench run with it is above every run of the parent commit (profiles/r33_a_kv_region.md).
+KV_REGION_DEFAULT = True
+KV_REGION_ENTRY = 'rmnet_conv_split_region_f32'
+KV_REGION_MAX_OBJECTS = 64       # csrc/conv_split.hip kRegionMaxObjects: more images per call go to the dense head
+
+
+def kv_region_enabled():
+    """RMNET_KV_REGION ('0' or '1', read at every call; unset: KV_REGION_DEFAULT).  Any other value is a RuntimeError."""
+    v = os.environ.get('RMNET_KV_REGION')
+    if v is None:
+        return KV_REGION_DEFAULT
+    if v.strip() not in ('0', '1'):
+        raise RuntimeError("RMNET_KV_REGION must be '0' or '1', got %r" % v)
+    return v.strip() == '1'
+
+
 def conv_split(x, wpack, w_unscale, shift=None, res=None, ksize=3, stride=1, relu_in=False, relu_out=False, out=None,
-               range_word=None, split=None, out_presplit=False):
+               range_word=None, split=None, out_presplit=False, rects=None, _out=None):
     """act(conv(pre(x), w) + shift + res) for a channels-last fp32 ``x`` [N, Cin, H, W], kernel ``ksize`` (1 or 3, padding
     ksize // 2), ``stride`` (1 or 2) and Cout = ``w_unscale.numel()`` (a multiple of 64) on the split-fp16 MFMA kernel
     (csrc/conv_split.hip); ``pre`` / ``act`` = ReLU when ``relu_in`` / ``relu_out``.  ``wpack, w_unscale`` come from
@@ -847,7 +865,12 @@ def conv_split(x, wpack, w_unscale, shift=None, res=None, ksize=3, stride=1, rel
     ``split_act`` or from ``out_presplit``); ``relu_in`` is then refused and nothing is counted for the input.  With
     ``out_presplit`` the result is returned in that form instead of fp32 (no ``out``, no ``split``) and its elements outside the
     window are counted in ``range_word``.  Same arithmetic and same bits either way.  No fall-back: anything else is a
-    RuntimeError."""
+    RuntimeError.
+
+    ``rects`` (int32 [N, 4] on the device: one cell rectangle (cx0, cx1, cy0, cy1) per image, inclusive, clamped to the map by the
+    kernel): the regional form, for a split-activation ``x``, ``ksize=3``, ``stride=1``, ``split=`` and Cout % 128 == 0.  The pair
+    is returned NCHW-contiguous; a cell inside its image's rectangle holds the bits of the call without ``rects``, every other
+    cell is +0.0.  Only the cells inside the rectangles are computed.  (``_out``: the pair to write, for the tests.)"""
     x_split = is_split_act(x)
     if x_split:
         _check_split_act(x, 'x')
@@ -881,7 +904,26 @@ def conv_split(x, wpack, w_unscale, shift=None, res=None, ksize=3, stride=1, rel
         if tuple(res.shape) != shape or not res.is_contiguous(memory_format=torch.channels_last):
             raise RuntimeError('res must be a channels-last %s tensor' % (shape,))
     out2 = None
-    if out_presplit:
+    if rects is not None:
+        if not x_split or ksize != 3 or stride != 1 or split is None or res is not None or out is not None or out_presplit \
+                or relu_in or cout % 128 or not 0 < split < cout or split % 4:
+            raise RuntimeError('conv_split: rects needs a split-activation x, ksize 3, stride 1, split= (a multiple of 4 in (0, Cout)) '
+                               'and Cout % 128 == 0, without res / out / out_presplit')
+        _check(rects, 'rects', torch.int32)
+        if tuple(rects.shape) != (N, 4):
+            raise RuntimeError('rects must be [N, 4] = %s, got %s' % ((N, 4), tuple(rects.shape)))
+        if _out is None:
+            out = torch.empty((N, split) + shape[2:], dtype=torch.float32, device=x.device)
+            out2 = torch.empty((N, cout - split) + shape[2:], dtype=torch.float32, device=x.device)
+        else:
+            out, out2 = _out
+            for t, c in ((out, split), (out2, cout - split)):
+                _check(t, '_out')
+                if tuple(t.shape) != (N, c) + shape[2:]:
+                    raise RuntimeError('_out must be the NCHW pair %s / %s' % ((N, split) + shape[2:], (N, cout - split) + shape[2:]))
+    elif _out is not None:
+        raise RuntimeError('conv_split: _out goes with rects')
+    elif out_presplit:
         if split is not None or out is not None:
             raise RuntimeError('conv_split: out_presplit returns one new split activation, without split / out')
         out = torch.empty((N, shape[2], shape[3], cout // 32, 2, 32), dtype=torch.float16, device=x.device)
@@ -898,10 +940,17 @@ def conv_split(x, wpack, w_unscale, shift=None, res=None, ksize=3, stride=1, rel
             raise RuntimeError('out must be a channels-last %s tensor' % (shape,))
     if range_word is not None:
         _check(range_word, 'range_word', torch.int32)
-    for t in (wpack, w_unscale, shift, res, out, range_word):
+    for t in (wpack, w_unscale, shift, res, out, out2, range_word, rects):
         if t is not None and t.device != x.device:
             raise RuntimeError('conv_split: every tensor must be on %s' % x.device)
     flags = (CONV_RELU_IN if relu_in else 0) | (CONV_RELU_OUT if relu_out else 0)
+    if rects is not None:
+        with torch.cuda.device(x.device):
+            rc = _lib.load().rmnet_conv_split_region_f32(_ptr(x), _ptr(wpack), _ptr(w_unscale), _ptr(shift), flags | CONV_X_SPLIT, N, H, W,
+                                                         cin, cout, ksize, stride, _ptr(rects), _ptr(out), _ptr(out2), split,
+                                                         _ptr(range_word), _stream(x.device))
+        _lib.check(rc, KV_REGION_ENTRY)
+        return out, out2
     # conv_rows: the switch on (read at every call, so a bad value raises whatever the shape), and the class it serves
     rows = trunk_rows_enabled() and x_split and ksize == 3 and stride == 1 and cin == cout and cin in TRUNK_ROWS_CLASSES \
         and res is None and split is None

@@ -227,11 +227,18 @@ class RMNet(nn.Module):
         if self.training:
             raise RuntimeError('rmnet_amd.RMNet is inference-only (its HIP kernels have no autograd): call .eval()')
 
-    def _encode_memory(self, frame, masks, n_objects):
+    def _encode_memory(self, frame, masks, n_objects, regional=False, flat=None):
         """EncoderMemory + KeyValue for every object in flight, and the boxes of the (padded)
-        masks as pixel boxes + cell rectangles.  K/V are returned UN-masked."""
+        masks as pixel boxes + cell rectangles.  K/V are returned UN-masked.
+
+        ``regional`` (the frame loop; ``flat`` = the clip's flat object indices): the heads get the objects' rectangles and may
+        compute only the cells inside them -- K/V are then NCHW and zero outside the boxes (``KeyValue.forward``) -- and the
+        object-order rectangles [no, 4] are returned as a fifth value."""
         B, K, H, W = masks.shape
         (frame, masks), _ = pad_divide_by([frame, masks.float()], 16, (H, W))
+        # (the boxes depend on the masks alone: in front of the encoder, so that the heads can use them)
+        _, bboxes, rects = ops.region_map(masks.contiguous(), want_map=False,
+                                          cell_grid=(0, 0, 16, masks.shape[2] // 16, masks.shape[3] // 16))
         if all(int(n) == 1 for n in n_objects):       # one object per clip: object i IS clip i, nothing to gather
             f_in, m_in = frame, masks[:, 1]
             o_in = None                               # (no other objects: EncoderMemory takes an all-zero plane)
@@ -249,9 +256,11 @@ class RMNet(nn.Module):
                         os_.append(others.clamp(0, 1))
             f_in, m_in, o_in = torch.cat(fs), torch.cat(ms), torch.cat(os_)
         r4 = self.encoder_memory(f_in, m_in, o_in)[0]
+        if regional:
+            obj_rects = rects.view(B * K, 4).index_select(0, flat)
+            k4, v4 = self.kv_memory(r4, obj_rects)
+            return k4, v4, bboxes, rects, obj_rects
         k4, v4 = self.kv_memory(r4)
-        h, w = k4.shape[-2:]
-        _, bboxes, rects = ops.region_map(masks.contiguous(), want_map=False, cell_grid=(0, 0, 16, h, w))
         return k4, v4, bboxes, rects
 
     @torch.no_grad()
@@ -281,13 +290,14 @@ class RMNet(nn.Module):
         return torch.log(em / (1 - em))
 
     def _segment_core(self, frame, qry_rects, m_key, m_val, mem_rects, T, n_objects, K, batch_of_obj,
-                      obj_begin=None):
+                      obj_begin=None, kv_rects=None):
         """Everything of ``segment`` after the box bookkeeping: query encoder, fused regional read,
         decoder, soft aggregation, un-pad.  With ``obj_begin`` (device int32 [B+1]) and
-        ``fuse_epilogues()`` the tail is one kernel and the return value is (logit, prob)."""
+        ``fuse_epilogues()`` the tail is one kernel and the return value is (logit, prob).  ``kv_rects`` (one rectangle per clip,
+        when object i is clip i): the query head may compute only the cells inside them (``KeyValue.forward``)."""
         (frame,), pad = pad_divide_by([frame], 16, frame.shape[2:])
         r4, r3, r2, _, _ = self.encoder_query(frame)
-        k4, v4 = self.kv_query(r4)
+        k4, v4 = self.kv_query(r4, kv_rects)
         if all(int(n) == 1 for n in n_objects):     # one object per clip: object i IS clip i, no expansion copies
             k4e, v4e, r3e, r2e = k4, v4, r3, r2
         else:
@@ -380,8 +390,16 @@ class RMNet(nn.Module):
         ``networks.set_split_conv_(net, False)``)."""
         self._inference_only()
         B, K = ctx.B, ctx.K
-        k4, v4, boxes, rects = self._encode_memory(prev_frame, prev_mask, ctx.n_max)
-        bank.stage(k4.contiguous(), v4.contiguous(), rects.view(B * K, 4).index_select(0, ctx.flat))
+        # RMNET_KV_REGION: the key / value heads on the cells inside the boxes (the bank stores nothing else, the read gathers the
+        # query keys by compacted cell and multiplies the query values by the box).  The memory head is per object and always
+        # regional; the query head is per clip, so only when every clip has one object (object i is clip i)
+        regional = ops.kv_region_enabled() and isinstance(bank, ops.MemoryBank)
+        if regional:
+            k4, v4, boxes, rects, obj_rects = self._encode_memory(prev_frame, prev_mask, ctx.n_max, regional=True, flat=ctx.flat)
+        else:
+            k4, v4, boxes, rects = self._encode_memory(prev_frame, prev_mask, ctx.n_max)
+            obj_rects = rects.view(B * K, 4).index_select(0, ctx.flat)
+        bank.stage(k4.contiguous(), v4.contiguous(), obj_rects)
         if getattr(self, '_fused_tail', False) and self._fused_warp_ok(prev_mask.device):   # warp fused into the box reduction
             _, _, q_rects = ops.region_map(prev_mask.contiguous(), want_map=False, flow=cur_flow.contiguous(),
                                            cell_grid=(ctx.lw, ctx.lh, 16, ctx.h, ctx.w))
@@ -391,7 +409,8 @@ class RMNet(nn.Module):
                                            cell_grid=(ctx.lw, ctx.lh, 16, ctx.h, ctx.w))
         q_rects = q_rects.view(B * K, 4).index_select(0, ctx.flat)
         out = self._segment_core(cur_frame, q_rects, bank, None, None, None, ctx.n_max, K, ctx.batch_of_obj,
-                                 obj_begin=ctx.obj_begin)
+                                 obj_begin=ctx.obj_begin,
+                                 kv_rects=q_rects if regional and all(int(n) == 1 for n in ctx.n_max) else None)
         if commit:          # AFTER the read: the frame count lives on the device (bank.n_dev), the read used committed + 1
             bank.commit()
         return out
