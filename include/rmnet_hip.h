@@ -784,6 +784,34 @@ int rmnet_clip_loss_f32(const float *probs, const uint8_t *labels, int N, int K,
                         double *per_class, double *nll_sum, long long *counts, void *workspace, size_t workspace_bytes,
                         void *stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * I2  Training loss of a clip, value and gradient: everything I1 returns and d(lovasz + nll) / d probs (additive exports, same
+ *     ABI version; csrc/val_loss_bwd.hip).
+ * Replaces: loss = lovasz_loss(est_probs, masks) + nll_loss(torch.log(est_probs), masks); loss.backward() of core/train.py:180,
+ *           as far as est_probs: no permuted copy, no sort, no int64 permutation, no index-scatter backward.
+ *   probs, labels, ignore_index, bins, per_class, nll_sum, counts: as in I1, and with the same bits as I1 returns.
+ *   grad         [N,K,H,W] float32 out, 4-byte aligned, not overlapping probs.  With key as in I1, G the class's foreground
+ *                count, F> / B> the sums of hist[c][1] / hist[c][0] over the bins above key and F>= / B>= those over the bins at or
+ *                above it, in float64 and rounded once to float32:
+ *                  g_fg[c][key] = (1 / (G + B>) + 1 / (G + B>=)) / 2
+ *                  g_bg[c][key] = (G - (F> + F>=) / 2) / ((G + B>) (G + B>=))               (both 0 for a class with G == 0)
+ *                and, in fp32 with one rounding per operation, s = -1 on a foreground element, +1 on a background one, 0 where
+ *                e == 0, n_present the classes with G > 0 and n_good = counts[0]:
+ *                  grad = (s * g) * (float)(1.0 / n_present)   [+ (float)(-1.0 / ((double)p * (double)n_good)) where c == label]
+ *                (-inf where p_label == 0).  All K elements of an ignored or bad pixel are 0.  This is the subgradient of the
+ *                Lovasz extension at the errors quantised to their bins: the mean of the two orders "the bin's foregrounds first"
+ *                and "the bin's backgrounds first"; it is the gradient of the reference's sort exactly where no bin of a class
+ *                holds more than one pixel, and within the span of the sort's possible tie orders everywhere.
+ *                Every element is written exactly once (the caller never pre-zeros); no atomics: the same bits from call to call.
+ *   workspace    8-byte aligned, at least rmnet_clip_loss_grad_workspace_bytes(K, bins) bytes.  When the call's work is complete
+ *                it begins with the tables, float32 [K][2][bins + 1] (index 0 = g_bg, 1 = g_fg), in the place of I1's hist.
+ * The refusals of I1, and RMNET_E_INVALID_ARG for a NULL or misaligned grad or one that overlaps probs.  Nothing is launched then.
+ * ------------------------------------------------------------------------------------------- */
+size_t rmnet_clip_loss_grad_workspace_bytes(int K, int bins);
+int rmnet_clip_loss_grad_f32(const float *probs, const uint8_t *labels, int N, int K, int H, int W, int ignore_index, int bins,
+                             float *grad, double *per_class, double *nll_sum, long long *counts, void *workspace,
+                             size_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

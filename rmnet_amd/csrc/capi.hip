@@ -333,4 +333,13 @@ int rmnet_clip_loss_f32(const float* probs, const uint8_t* labels, int N, int K,
                           static_cast<hipStream_t>(stream));
 }
 
+size_t rmnet_clip_loss_grad_workspace_bytes(int K, int bins) { return clip_loss_grad_ws_bytes(K, bins); }
+
+int rmnet_clip_loss_grad_f32(const float* probs, const uint8_t* labels, int N, int K, int H, int W, int ignore_index, int bins,
+                             float* grad, double* per_class, double* nll_sum, long long* counts, void* workspace,
+                             size_t workspace_bytes, void* stream) {
+  return launch_clip_loss_grad(probs, labels, N, K, H, W, ignore_index, bins, grad, per_class, nll_sum, counts, workspace,
+                               workspace_bytes, static_cast<hipStream_t>(stream));
+}
+
 }  // extern "C"

@@ -453,6 +453,10 @@ int launch_object_edit_softmax_nearest(float* logit, long long logit_bs, const u
 size_t clip_loss_ws_bytes(int K, int bins);
 int launch_clip_loss(const float* probs, const uint8_t* labels, int N, int K, int H, int W, int ignore_index, int bins, double* per_class,
                      double* nll_sum, long long* counts, void* ws, size_t ws_bytes, hipStream_t st);
+// val_loss_bwd.hip: the same outputs and the gradient of lovasz + nll with respect to the probabilities
+size_t clip_loss_grad_ws_bytes(int K, int bins);
+int launch_clip_loss_grad(const float* probs, const uint8_t* labels, int N, int K, int H, int W, int ignore_index, int bins, float* grad,
+                          double* per_class, double* nll_sum, long long* counts, void* ws, size_t ws_bytes, hipStream_t st);
 
 inline int check_launch() { return hipGetLastError() == hipSuccess ? RMNET_OK : RMNET_E_LAUNCH; }
 

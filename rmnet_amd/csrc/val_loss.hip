@@ -36,39 +36,12 @@
 // and the lane adds its float64 terms from its top bin down; lanes, then waves, are reduced in a fixed order.  Workgroup 0 also
 // adds the NLL partials and the pixel counters in workgroup order.  Plain stores only; no static LDS (dynamic, sized at launch).
 // The histogram is cleared by a memset in front of vl_hist (a memset node under capture): the caller never pre-zeros.
-#include "common.h"
+#include "val_loss_parts.h"
 
 namespace rmnet {
 namespace {
 
-typedef unsigned int u32;
-
-constexpr int kHistThreads = 512;
-constexpr int kHistWaves = kHistThreads / RMNET_WAVE;
-constexpr int kMaxBlocks = 512;
-constexpr int kLdsWords = 15872;                  // 62 KB of privatised bins
-constexpr int kScanThreads = 1024;
-constexpr int kScanWaves = kScanThreads / RMNET_WAVE;
-constexpr int kRun = 16;                          // consecutive bins per lane and step of vl_scan's second pass
-constexpr int kMinBins = 2, kMaxBins = 1 << 22;
-
-inline bool bins_ok(int bins) { return bins >= kMinBins && bins <= kMaxBins && (bins & (bins - 1)) == 0; }
-
-// the bins kept in LDS: [0, LB) and [bins + 1 - HB, bins]
-inline void lds_bins(int K, int bins, int* LB, int* HB) {
-  int s = 1;
-  while (2 * s * 2 * K <= kLdsWords) s *= 2;
-  if (bins + 1 <= s) { *LB = bins + 1; *HB = 0; } else { *LB = s / 2; *HB = s / 2; }
-}
-
-inline size_t hist_words(int K, int bins) { return (size_t)K * 2 * ((size_t)bins + 1); }
-inline size_t partial_offset(int K, int bins) { return (hist_words(K, bins) * sizeof(u32) + 7) & ~(size_t)7; }
-
-__device__ inline double wave_sum_f64(double v) {      // xor tree: the same order in every call
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
+using namespace vl;      // the layout, the LDS rule and the wave reductions are shared with val_loss_bwd.hip
 
 extern __shared__ __align__(8) unsigned char vl_dyn[];
 
@@ -213,16 +186,6 @@ __global__ __launch_bounds__(kHistThreads) void vl_hist(const float* __restrict_
   }
 }
 
-// inclusive suffix sum over the wave: lane l gets the sum of lanes l .. 63
-__device__ inline u32 wave_suffix(u32 v, int lane) {
-#pragma unroll
-  for (int o = 1; o < RMNET_WAVE; o <<= 1) {
-    const u32 t = __shfl_down(v, o);
-    if (lane + o < RMNET_WAVE) v += t;
-  }
-  return v;
-}
-
 __global__ __launch_bounds__(kScanThreads) void vl_scan(const u32* __restrict__ hist, const double* __restrict__ part_nll,
                                                         const long long* __restrict__ part_cnt, int n_blocks, int bins,
                                                         double* __restrict__ per_class, double* __restrict__ nll_sum,
@@ -300,8 +263,8 @@ size_t clip_loss_ws_bytes(int K, int bins) {
   return partial_offset(K, bins) + (size_t)kMaxBlocks * (sizeof(double) + 3 * sizeof(long long));
 }
 
-int launch_clip_loss(const float* probs, const uint8_t* labels, int N, int K, int H, int W, int ignore_index, int bins, double* per_class,
-                     double* nll_sum, long long* counts, void* ws, size_t ws_bytes, hipStream_t st) {
+int launch_clip_hist(const float* probs, const uint8_t* labels, int N, int K, int H, int W, int ignore_index, int bins, double* per_class,
+                     double* nll_sum, long long* counts, void* ws, size_t ws_bytes, hipStream_t st, int* n_blocks) {
   if (!probs || !labels || !per_class || !nll_sum || !counts || N <= 0 || H <= 0 || W <= 0) return RMNET_E_INVALID_ARG;
   if (K < 1 || K > 255 || !bins_ok(bins)) return RMNET_E_INVALID_ARG;
   const long long HW = (long long)H * W, P = HW * N;
@@ -316,18 +279,26 @@ int launch_clip_loss(const float* probs, const uint8_t* labels, int N, int K, in
   u32* hist = static_cast<u32*>(ws);
   double* part_nll = reinterpret_cast<double*>(static_cast<unsigned char*>(ws) + partial_offset(K, bins));
   long long* part_cnt = reinterpret_cast<long long*>(part_nll + kMaxBlocks);
-  const long long groups = (P + 3) / 4;
-  long long blocks = (groups + kHistThreads - 1) / kHistThreads;
-  if (blocks > kMaxBlocks) blocks = kMaxBlocks;
-  long long per_block = (groups + blocks - 1) / blocks;
-  per_block = (per_block + kHistThreads - 1) / kHistThreads * kHistThreads;              // whole steps: a wave's groups stay contiguous
-  blocks = (groups + per_block - 1) / per_block;
+  long long groups, blocks, per_block;
+  stream_grid(P, &groups, &blocks, &per_block);
   if (hipMemsetAsync(hist, 0, hist_words(K, bins) * sizeof(u32), st) != hipSuccess) return RMNET_E_LAUNCH;
   const size_t lds1 = (size_t)K * 2 * (LB + HB) * sizeof(u32) + kHistWaves * (sizeof(double) + 3 * sizeof(long long));
   hipLaunchKernelGGL(vl_hist, dim3((unsigned)blocks), dim3(kHistThreads), lds1, st, probs, labels, hist, part_nll, part_cnt, P, HW, K,
                      ignore, bins, LB, HB, groups, per_block);
+  *n_blocks = (int)blocks;
+  return RMNET_OK;
+}
+
+int launch_clip_loss(const float* probs, const uint8_t* labels, int N, int K, int H, int W, int ignore_index, int bins, double* per_class,
+                     double* nll_sum, long long* counts, void* ws, size_t ws_bytes, hipStream_t st) {
+  int blocks = 0;
+  const int rc = launch_clip_hist(probs, labels, N, K, H, W, ignore_index, bins, per_class, nll_sum, counts, ws, ws_bytes, st, &blocks);
+  if (rc != RMNET_OK) return rc;
+  const u32* hist = static_cast<const u32*>(ws);
+  const double* part_nll = reinterpret_cast<const double*>(static_cast<const unsigned char*>(ws) + partial_offset(K, bins));
+  const long long* part_cnt = reinterpret_cast<const long long*>(part_nll + kMaxBlocks);
   const size_t lds2 = kScanWaves * 2 * (sizeof(double) + sizeof(u32));
-  hipLaunchKernelGGL(vl_scan, dim3((unsigned)K), dim3(kScanThreads), lds2, st, hist, part_nll, part_cnt, (int)blocks, bins, per_class,
+  hipLaunchKernelGGL(vl_scan, dim3((unsigned)K), dim3(kScanThreads), lds2, st, hist, part_nll, part_cnt, blocks, bins, per_class,
                      nll_sum, counts);
   return check_launch();
 }

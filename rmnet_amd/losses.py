@@ -16,6 +16,10 @@ Two routes compute it.
   The errors are the fp32 values; counts, indices and the sum are float64, so lo == hi == the sorted value up to float64
   rounding.  It runs on CPU tensors and is the A/B yardstick on the device, where its masked selection synchronises.
 
+``training_loss`` is the same loss, differentiable once with respect to ``probs`` (core/train.py:180): on 'hip' an
+autograd.Function around ``ops.clip_loss_grad`` (csrc/val_loss_bwd.hip), whose one histogram pass gives value and gradient; on
+'torch' autograd through the sort.  The three functions under ``torch.no_grad`` are unchanged by it.
+
 Both leave the same pixels out: a pixel whose label is ``ignore_index``; and, counted in ``n_bad``, a pixel whose label is >= K
 or that has a probability outside [0, 1] (NaN included) -- torch's NLLLoss would raise for the former, and a NaN that silently
 turns finite has been met here before (profiles/r14_a_glue_tests.md).
@@ -130,3 +134,89 @@ def validation_loss(probs, labels, ignore_index=255, bins=DEFAULT_BINS, route=No
     lovasz = _lovasz_from(pieces['per_class'])['value']
     nll_value = _nll_from(pieces)
     return {'loss': lovasz + nll_value, 'lovasz': lovasz, 'nll': nll_value, 'n_bad': pieces['counts'][1] + pieces['counts'][2]}
+
+
+# ------------------------------------------------------------------------------------------------ the training loss
+# The route that CUDA tensors take through ``training_loss`` by default, forward + backward.  Measured on an MI355X
+# (profiles/r34_a_loss_grad.md; HIP events, 20 / 5 calls back to back, 'hip' against 'torch'), 70-frame 480 x 854 clip at 2^20 bins:
+# 3.56 against 29.87 ms with K = 3 and 9.64 against 86.77 ms with K = 11 on synthetic peaked soft-maxes, 5.06 against 30.11 ms and 10.56
+# against 58.40 ms on the saturated output of RMNet.forward with procedural weights; a training batch of the reference's config.py
+# (12 x 4 x 465 x 465) 2.91 against 3.65 ms.  At 2^12 bins: 0.79 / 2.16 ms (synthetic), 21.69 / 36.26 ms (saturated: vl_hist's
+# contended LDS adds) and 0.37 ms (batch), all below the sort's.  Peak memory above the inputs, K = 3 / K = 11: 0.69 / 2.53 GB (the
+# saved gradient and its product with grad_output) against 3.99 / 9.50 GB.  'hip' is faster in every case, so no K is routed to 'torch'.
+TRAIN_DEVICE_ROUTE = 'hip'
+
+
+def _check_training(probs, labels, route):
+    if probs.dim() != 4 or labels.dim() != 3 or (probs.shape[0],) + tuple(probs.shape[2:]) != tuple(labels.shape):
+        raise RuntimeError('expected probs [N, K, H, W] and labels [N, H, W]')
+    if labels.dtype != torch.uint8:
+        raise RuntimeError('expected uint8 labels')
+    if probs.dtype != torch.float32 and not (route == 'torch' and probs.dtype == torch.float64):
+        raise RuntimeError("expected float32 probabilities (float64 too on the 'torch' route)")
+
+
+def _torch_training_loss(probs, labels, ignore_index):
+    """The sort, left differentiable: the permutation and the Jaccard steps carry no gradient (models/lovasz_loss.py detaches the
+    permutation and computes the steps from the labels alone), abs has derivative 0 at 0, and the NLL is -log(p_label) / good
+    pixels.  Steps and sums are float64."""
+    K = probs.shape[1]
+    good, _, _ = _pixel_classes(probs.detach(), labels, ignore_index)
+    p = probs.permute(0, 2, 3, 1)[good]                           # [P, K], the good pixels only
+    lab = labels[good].long()
+    terms = []
+    for c in range(K):
+        fg = lab == c
+        G = fg.sum().to(torch.float64)
+        if float(G) == 0:
+            continue
+        e, order = torch.sort((fg.to(p.dtype) - p[:, c]).abs(), descending=True)
+        fg_sorted = fg[order].to(torch.float64)
+        f = fg_sorted.cumsum(0)
+        b = (1.0 - fg_sorted).cumsum(0)
+        jac = 1.0 - (G - f) / (G + b)
+        step = jac.clone()
+        step[1:] = jac[1:] - jac[:-1]
+        terms.append((e.to(torch.float64) * step).sum())
+    lovasz = torch.stack(terms).sum() / len(terms) if terms else p.to(torch.float64).sum() * 0.0
+    p_label = p.gather(1, lab.view(-1, 1)).view(-1) if lab.numel() else p.new_zeros(0)
+    nll_sum = -(p_label.to(torch.float64).log()).sum()
+    return lovasz + nll_sum / good.sum().to(torch.float64)      # 0 / 0 = NaN with no pixel, as NLLLoss gives
+
+
+class _TrainingLossHip(torch.autograd.Function):
+    """Value and gradient from one call of ``ops.clip_loss_grad``: the histogram is built once."""
+
+    @staticmethod
+    def forward(ctx, probs, labels, ignore_index, bins):
+        from . import ops
+        out = ops.clip_loss_grad(probs.contiguous(), labels.contiguous(), ignore_index, bins)
+        ctx.save_for_backward(out['grad'])
+        return _lovasz_from(out['per_class'])['value'] + _nll_from(out)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_output):
+        grad, = ctx.saved_tensors
+        return grad * grad_output.to(grad.dtype), None, None, None
+
+
+def training_loss(probs, labels, ignore_index=255, bins=DEFAULT_BINS, route=None):
+    """lovasz + nll of core/train.py:180 as a float64 0-d tensor on the device of ``probs``, differentiable once with respect to
+    ``probs`` (the soft-max in front of them is the network's).  On 'hip' the gradient is the subgradient at the errors quantised
+    to ``bins`` bins (csrc/val_loss_bwd.hip): that of the sort where no bin of a class holds two pixels, inside the span of the
+    sort's tie orders elsewhere; ignored and bad pixels get 0.  When nothing asks for a gradient the forward entry runs alone."""
+    if not probs.is_cuda:
+        route = 'torch'
+    else:
+        route = TRAIN_DEVICE_ROUTE if route is None else route
+        if route not in ('hip', 'torch'):
+            raise ValueError("route must be 'hip' or 'torch'")
+    _check_training(probs, labels, route)
+    if route == 'torch':
+        return _torch_training_loss(probs, labels, ignore_index)
+    if probs.requires_grad and torch.is_grad_enabled():
+        return _TrainingLossHip.apply(probs, labels, int(ignore_index), int(bins))
+    from . import ops
+    pieces = ops.clip_loss(probs.detach().contiguous(), labels.contiguous(), ignore_index, bins)
+    return _lovasz_from(pieces['per_class'])['value'] + _nll_from(pieces)

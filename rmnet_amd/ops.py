@@ -1483,6 +1483,38 @@ def clip_loss(probs, labels, ignore_index=255, bins=1 << 20, want_hist=False):
     return out
 
 
+def clip_loss_grad(probs, labels, ignore_index=255, bins=1 << 20, want_tables=False):
+    """``clip_loss`` and the gradient of the training loss lovasz + nll of core/train.py:180 with respect to ``probs``, from one
+    histogram pass (csrc/val_loss_bwd.hip, include/rmnet_hip.h I2), as device tensors and without a sync: 'per_class', 'nll_sum' and
+    'counts' with the bits ``clip_loss`` gives them, and
+      'grad'      float32 [N,K,H,W]: s * g_kind[c][key] / n_present, plus -1 / (p_label * n_good) on the label's channel; 0 in every
+                  channel of an ignored or bad pixel.  Every element is written: nothing is pre-zeroed.
+      'tables'    with want_tables, float32 [K,2,bins+1]: g_bg (index 0) and g_fg (index 1) per class and bin (a view of the call's
+                  workspace)."""
+    _check(probs, 'probs')
+    _check(labels, 'labels', dtype=torch.uint8)
+    if probs.dim() != 4 or labels.dim() != 3 or (probs.shape[0],) + tuple(probs.shape[2:]) != tuple(labels.shape):
+        raise RuntimeError('expected probs [N, K, H, W] and labels [N, H, W]')
+    if labels.device != probs.device:
+        raise RuntimeError('probs and labels must be on the same device')
+    lib = _lib.load()
+    N, K, H, W = probs.shape
+    bins, dev = int(bins), probs.device
+    with torch.cuda.device(dev):
+        grad = torch.empty(N, K, H, W, dtype=torch.float32, device=dev)
+        per_class = torch.empty(max(K, 1), 3, dtype=torch.float64, device=dev)
+        nll_sum = torch.empty((), dtype=torch.float64, device=dev)
+        counts = torch.empty(3, dtype=torch.int64, device=dev)
+        ws = _ws(lib.rmnet_clip_loss_grad_workspace_bytes(K, bins), dev)
+        rc = lib.rmnet_clip_loss_grad_f32(_ptr(probs), _ptr(labels), N, K, H, W, int(ignore_index), bins, _ptr(grad), _ptr(per_class),
+                                          _ptr(nll_sum), _ptr(counts), _ptr(ws), ws.numel(), _stream(dev))
+    _lib.check(rc, 'rmnet_clip_loss_grad_f32')
+    out = {'per_class': per_class, 'nll_sum': nll_sum, 'counts': counts, 'grad': grad}
+    if want_tables:
+        out['tables'] = ws[:K * 2 * (bins + 1) * 4].view(torch.float32).view(K, 2, bins + 1)
+    return out
+
+
 # ------------------------------------------------------------------------------------------------ clip I/O (csrc/clip_io.hip)
 def _three_doubles(v, name):
     v = [float(x) for x in v]
