@@ -550,6 +550,34 @@ int rmnet_soft_aggregate_f32(const float *dec, const int32_t *obj_begin, int B, 
                              int pad_l, int pad_t, int H, int W, float *logit, float *prob,
                              void *stream);
 
+/* The gradient of that tail with respect to dec (additive export, same ABI version; csrc/soft_aggregate_bwd.hip), one streaming
+ * pass: the backward of the soft-max over K (models/rmnet.py:450), of the edits of :436-448 (rmnet_object_edit_softmax_f32), of
+ * the un-pad, of soft_aggregation and of F.softmax(dec, dim=1)[:, 1].  Per clip b with n = min(obj_begin[b+1] - obj_begin[b],
+ * K - 1) objects and per output pixel, with p_o and bg the forward's fp32 values (re-created from dec by the forward's own code):
+ *   s    = sum_k P_k g_k over all K channels, in channel order;   dl_k = P_k (g_k - s) + q_k
+ *   live_k = k <= n and action[b][k] == 0;   pass(e) = 1e-7f <= e <= 1 - 1e-7f (ends inside as in torch.clamp, false for a NaN)
+ *   a0   = live_0 and pass(bg) ? dl_0 / (1 - bg) : 0;   dz_o = (live_{o+1} and pass(p_o) ? dl_{o+1} : 0) - a0 p_o
+ *   grad_dec[obj_begin[b] + o][1] = dz_o,  grad_dec[obj_begin[b] + o][0] = -dz_o          every operation rounded once, no FMA
+ *   prob        P, the saved final probabilities [B,K,H,W] (after the edits on an edited frame), batch-strided like
+ *               rmnet_object_edit_softmax_f32's: slice b starts at prob + b * prob_batch_stride and is contiguous
+ *   grad_prob   g = d loss / d P, batch-strided likewise; may be NULL when grad_logit is given (then dl_k = q_k, P is not read)
+ *   grad_logit  q = d loss / d logit (the logits after the edits), batch-strided likewise; may be NULL when grad_prob is given
+ *   action      uint8 [B,K] as in rmnet_object_edit_softmax_f32 (0 keep, 1 absent, 2 inject), or NULL = every channel kept
+ *   grad_dec    [n_tot,2,Hp,Wp]: EVERY element is written exactly once -- +0.0 in the padding rows and columns and for the objects
+ *               o >= n of a clip with more than K - 1 objects -- so it needs no memset; no atomics, the same bits on every call.
+ *               obj_begin[0] must be 0.
+ * A NaN in dec makes P and therefore dl NaN at its pixel: every object of the clip whose channel or whose background passes gets a
+ * NaN there, an object behind two masks gets 0, none gets a finite non-zero value.
+ * Lane forms: 4 pixels per lane when Wp % 4 == 0 and dec, grad_dec are 16-byte aligned (prob / grad_prob / grad_logit are then read
+ * with 16-byte loads too when W % 4 == 0, pad_l % 4 == 0, they are 16-byte aligned and their strides are multiples of 4), else 1.
+ * RMNET_E_INVALID_ARG: a NULL dec, obj_begin, prob or grad_dec; grad_prob and grad_logit both NULL; a float pointer that is not
+ * 4-byte aligned; B, K, H or W < 1; K > 255; pad_l or pad_t < 0; pad_l + W > Wp or pad_t + H > Hp; a given batch stride < K*H*W.
+ * RMNET_E_UNSUPPORTED: B > 65535; 2*Hp*Wp, K*H*W, a stride or (B-1)*stride + K*H*W >= 2^31.  A refused call touches no buffer. */
+int rmnet_soft_aggregate_bwd_f32(const float *dec, const int32_t *obj_begin, int B, int K, int Hp, int Wp, int pad_l, int pad_t, int H,
+                                 int W, const float *prob, long long prob_batch_stride, const float *grad_prob,
+                                 long long grad_prob_batch_stride, const float *grad_logit, long long grad_logit_batch_stride,
+                                 const uint8_t *action, float *grad_dec, void *stream);
+
 /* ---------------------------------------------------------------------------------------------
  * F1  Optical-flow update after two affine warps.
  * Replaces: CPython `flow_affine_transformation.update_optical_flow(flow, M1, M2)` --

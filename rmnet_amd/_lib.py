@@ -79,6 +79,9 @@ SIGNATURES = {
     'rmnet_soft_aggregate_f32': (ctypes.c_int, [
         c_f32p, c_i32p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
         ctypes.c_int, ctypes.c_int, c_f32p, c_f32p, ctypes.c_void_p]),
+    'rmnet_soft_aggregate_bwd_f32': (ctypes.c_int, [
+        c_f32p, c_i32p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+        c_f32p, ctypes.c_longlong, c_f32p, ctypes.c_longlong, c_f32p, ctypes.c_longlong, ctypes.c_void_p, c_f32p, ctypes.c_void_p]),
     'rmnet_affine_relu_maxpool_f32': (ctypes.c_int, [
         c_f32p, c_f32p, c_f32p, ctypes.c_longlong, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_f32p,
         ctypes.c_void_p]),

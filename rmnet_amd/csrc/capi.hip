@@ -191,6 +191,13 @@ int rmnet_soft_aggregate_f32(const float* dec, const int32_t* obj_begin, int B, 
                                static_cast<hipStream_t>(stream));
 }
 
+int rmnet_soft_aggregate_bwd_f32(const float* dec, const int32_t* obj_begin, int B, int K, int Hp, int Wp, int pad_l, int pad_t, int H,
+                                 int W, const float* prob, long long prob_bs, const float* grad_prob, long long grad_prob_bs,
+                                 const float* grad_logit, long long grad_logit_bs, const uint8_t* action, float* grad_dec, void* stream) {
+  return launch_soft_aggregate_bwd(dec, obj_begin, B, K, Hp, Wp, pad_l, pad_t, H, W, prob, prob_bs, grad_prob, grad_prob_bs, grad_logit,
+                                   grad_logit_bs, action, grad_dec, static_cast<hipStream_t>(stream));
+}
+
 int rmnet_region_map_warped_f32(const float* mask, const float* flow, int B, int K, int H, int W,
                                 float prob_threshold, int n_pts_threshold, int n_bbox_loose_pixels,
                                 float* att_map, int32_t* bboxes, int32_t* cell_rects, int pad_l,

@@ -458,6 +458,11 @@ size_t clip_loss_grad_ws_bytes(int K, int bins);
 int launch_clip_loss_grad(const float* probs, const uint8_t* labels, int N, int K, int H, int W, int ignore_index, int bins, float* grad,
                           double* per_class, double* nll_sum, long long* counts, void* ws, size_t ws_bytes, hipStream_t st);
 
+// soft_aggregate_bwd.hip: the gradient of soft_aggregate (+ the edits and the soft-max of lo_edit) with respect to the decoder logits
+int launch_soft_aggregate_bwd(const float* dec, const int32_t* obj_begin, int B, int K, int Hp, int Wp, int pad_l, int pad_t, int H, int W,
+                              const float* prob, long long prob_bs, const float* grad_prob, long long grad_prob_bs, const float* grad_logit,
+                              long long grad_logit_bs, const uint8_t* action, float* grad_dec, hipStream_t st);
+
 inline int check_launch() { return hipGetLastError() == hipSuccess ? RMNET_OK : RMNET_E_LAUNCH; }
 
 }  // namespace rmnet

@@ -14,6 +14,8 @@
 
 #pragma clang fp contract(off)   // x*scale + shift rounds like the two torch ops it replaces
 
+#include "soft_aggregate_parts.h"
+
 namespace rmnet {
 namespace {
 
@@ -144,17 +146,10 @@ __global__ __launch_bounds__(kThreads) void upsample2x_add(const float* __restri
 //   dec [n_tot, 2, Hp, Wp] decoder logits of the objects in flight, clip b owning objects
 //   [obj_begin[b], obj_begin[b+1]);  outputs [B, K, H, W] (channel 0 = background, 1..n = objects,
 //   the rest absent: em = 0 -> clamp -> logit = log(1e-7 / (1 - 1e-7))).
-__device__ inline float fg_prob(const float* __restrict__ dec, size_t plane, size_t pix) {
-  const float z0 = dec[pix], z1 = dec[plane + pix];
-  const float m = fmaxf(z0, z1);
-  const float e0 = expf(z0 - m), e1 = expf(z1 - m);
-  return e1 / (e0 + e1);
-}
+// fg_prob and the clamp live in soft_aggregate_parts.h: the gradient (soft_aggregate_bwd.hip) re-creates p and bg from them.
+using sa::fg_prob;
 __device__ inline float em_logit(float em) {
-  // comparisons, not fmaxf / fminf: those return the other operand for a NaN, which turned a NaN probability into the
-  // absent-channel logit; torch.clamp (models/rmnet.py:300) keeps it
-  em = em < 1e-7f ? 1e-7f : em;
-  em = em > 1.0f - 1e-7f ? 1.0f - 1e-7f : em;
+  em = sa::clamp_em(em);
   return logf(em / (1.0f - em));
 }
 

@@ -591,10 +591,99 @@ def upsample2x_add(x, skip=None, out=None):
     return out
 
 
-def soft_aggregate(dec, obj_begin, K, pad, want_prob=False):
+def soft_aggregate_backward(dec, obj_begin, K, pad, prob, grad_prob=None, grad_logit=None, action=None):
+    """The gradient of the decoder tail with respect to ``dec`` [n_tot,2,Hp,Wp], in one launch (csrc/soft_aggregate_bwd.hip,
+    include/rmnet_hip.h: rmnet_soft_aggregate_bwd_f32).  ``prob`` [B,K,H,W] are the probabilities the forward saved (after the
+    edits on an edited frame), ``grad_prob`` / ``grad_logit`` the gradients with respect to them / to the (edited) logits -- at
+    least one --, ``action`` uint8 [B,K] the frame's edits (``object_edit_softmax``) or None.  prob and the two gradients may be
+    batch-strided views whose slices are contiguous (``est[:, t]``).  Returns ``grad_dec`` like ``dec``, every element written."""
+    _check(dec, 'dec')
+    _check(obj_begin, 'obj_begin', torch.int32)
+    if dec.dim() != 4 or dec.shape[1] != 2:
+        raise RuntimeError('dec must be [n,2,Hp,Wp]')
+    if grad_prob is None and grad_logit is None:
+        raise RuntimeError('soft_aggregate_backward needs grad_prob or grad_logit')
+    B = obj_begin.numel() - 1
+    K = int(K)
+    if B < 1 or not 1 <= K <= 255:
+        raise RuntimeError('expected obj_begin [B+1] with B >= 1 and 1 <= K <= 255')
+    Hp, Wp = dec.shape[2:]
+    lw, uw, lh, uh = pad
+    H, W = Hp - lh - uh, Wp - lw - uw
+    strides = []
+    for t, name in ((prob, 'prob'), (grad_prob, 'grad_prob'), (grad_logit, 'grad_logit')):
+        if t is None:
+            strides.append(0)
+            continue
+        strides.append(_batch_slices(t, name, (K, H, W), torch.float32))
+        if t.shape[0] != B or t.device != dec.device:
+            raise RuntimeError('%s must be [B, K, H, W] on the device of dec' % name)
+    if action is not None:
+        _check(action, 'action', dtype=torch.uint8)
+        if tuple(action.shape) != (B, K) or action.device != dec.device:
+            raise RuntimeError('action must be uint8 [B, K] on the device of dec')
+    grad_dec = torch.empty_like(dec)
+    if dec.numel() == 0:
+        return grad_dec
+    lib = _lib.load()
+    with torch.cuda.device(dec.device):
+        rc = lib.rmnet_soft_aggregate_bwd_f32(_ptr(dec), _ptr(obj_begin), B, K, Hp, Wp, lw, lh, H, W, _ptr(prob), strides[0],
+                                              _ptr(grad_prob), strides[1], _ptr(grad_logit), strides[2], _ptr(action), _ptr(grad_dec),
+                                              _stream(dec.device))
+    _lib.check(rc, 'rmnet_soft_aggregate_bwd_f32')
+    return grad_dec
+
+
+class _SoftAggregateFn(torch.autograd.Function):
+    """soft_aggregate (+ object_edit_softmax on an edited frame) under autograd: the forward is the two launches every other caller
+    makes, the backward is soft_aggregate_backward.  It returns (logit, prob) and both are differentiable."""
+
+    @staticmethod
+    def forward(ctx, dec, obj_begin, K, pad, edit):
+        d = dec.detach()
+        logit, prob = soft_aggregate(d, obj_begin, K, pad, want_prob=True)
+        action = None
+        if edit is not None:
+            labels, lut, action = edit[:3]
+            object_edit_softmax(logit, labels, lut, action, prob, edit[3] if len(edit) > 3 else None)
+        ctx.save_for_backward(dec, obj_begin, prob, *(() if action is None else (action,)))
+        ctx.K, ctx.pad = K, tuple(pad)
+        ctx.set_materialize_grads(False)
+        return logit, prob
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_logit, grad_prob):
+        saved = ctx.saved_tensors
+        dec, obj_begin, prob = saved[:3]
+        if grad_logit is None and grad_prob is None:
+            return None, None, None, None, None
+        same = lambda g: None if g is None else g.contiguous()         # (an expanded or sliced grad_output becomes a plain tensor)
+        grad = soft_aggregate_backward(dec.detach(), obj_begin, ctx.K, ctx.pad, prob, same(grad_prob), same(grad_logit),
+                                       saved[3] if len(saved) > 3 else None)
+        return grad, None, None, None, None
+
+
+def soft_aggregate(dec, obj_begin, K, pad, want_prob=False, edit=None):
     """Decoder logits [n_tot,2,Hp,Wp] -> (logit [B,K,H,W], prob [B,K,H,W] | None): 2-class soft-max,
     soft aggregation (models/rmnet.py:289-302), un-pad by ``pad = (lw, uw, lh, uh)`` and, when asked,
-    the soft-max over the K channels, in one kernel.  ``obj_begin`` int32 [B+1] on the device."""
+    the soft-max over the K channels, in one kernel.  ``obj_begin`` int32 [B+1] on the device.
+
+    ``edit = (labels, lut, action[, sampling])``: the frame's late-object edits (models/rmnet.py:436-448) follow in a second
+    launch -- the arguments of ``object_edit_softmax`` -- so the returned logits are the edited ones and ``prob`` their soft-max.
+
+    Differentiable in ``dec``: when grad mode is on and ``dec`` requires grad, the call is recorded as one
+    ``torch.autograd.Function`` whose backward is ``soft_aggregate_backward`` (one launch).  The probabilities are then computed
+    whether or not they are asked for -- the backward reads them --, and there is no double backward.  Every other call takes
+    the plain path."""
+    if isinstance(dec, torch.Tensor) and dec.requires_grad and torch.is_grad_enabled():
+        _check(dec, 'dec')
+        logit, prob = _SoftAggregateFn.apply(dec, obj_begin, K, pad, edit)
+        return logit, (prob if want_prob else None)
+    if edit is not None:
+        logit, prob = soft_aggregate(dec, obj_begin, K, pad, want_prob=True)
+        object_edit_softmax(logit, edit[0], edit[1], edit[2], prob, edit[3] if len(edit) > 3 else None)
+        return logit, (prob if want_prob else None)
     _check(dec, 'dec')
     _check(obj_begin, 'obj_begin', torch.int32)
     if dec.dim() != 4 or dec.shape[1] != 2:

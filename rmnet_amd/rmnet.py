@@ -289,6 +289,44 @@ class RMNet(nn.Module):
         em = torch.clamp(em, 1e-7, 1 - 1e-7)
         return torch.log(em / (1 - em))
 
+    def decoder_tail(self, dec, n_objects, K, pad, edit=None):
+        """Everything between the decoder and the loss, differentiable in ``dec`` and usable in training mode: decoder logits
+        [n_tot,2,Hp,Wp] of the objects in flight, clip b owning ``n_objects[b]`` of them in order (a list of ints) -> (logit, prob)
+        [B,K,H,W]: F.softmax(dec, dim=1)[:, 1], ``soft_aggregation``, the un-pad by ``pad = (lw, uw, lh, uh)``, the late-object
+        edits of models/rmnet.py:436-448 when ``edit = (labels, lut, action[, sampling])`` is given (the arguments of
+        ``object_plan.object_edit_softmax``), and the soft-max over the K channels (:450).
+
+        On a CUDA tensor this is ``ops.soft_aggregate``: one launch (two on an edited frame) forward and one launch backward
+        (csrc/soft_aggregate_bwd.hip).  On the CPU it is the module graph, which autograd handles by itself; there a clip may not
+        hold more than K - 1 objects (the kernel caps the count, ``soft_aggregation`` cannot)."""
+        n_objects = [int(n) for n in n_objects]
+        if dec.is_cuda:
+            begin = [0]
+            for n in n_objects:
+                begin.append(begin[-1] + n)
+            obj_begin = torch.tensor(begin, dtype=torch.int32, device=dec.device)
+            return ops.soft_aggregate(dec.contiguous(), obj_begin, K, pad, want_prob=True, edit=edit)
+        ps = F.softmax(dec, dim=1)[:, 1]
+        logit = self.soft_aggregation(ps, K, n_objects)
+        lw, uw, lh, uh = pad
+        logit = logit[:, :, lh:logit.shape[2] - uh, lw:logit.shape[3] - uw]
+        if edit is not None:
+            from . import object_plan
+            labels, lut, action = edit[:3]
+            if len(edit) > 3 and edit[3] is not None and labels is not None:
+                s = edit[3]
+                labels = object_plan._sample_labels(labels, logit.shape[2], logit.shape[3], (float(s[0]), float(s[1]), [bool(f) for f in s[2]]))
+            logit = logit.clone()
+            act = action.detach().cpu().numpy()
+            for b in range(act.shape[0]):
+                for k in range(act.shape[1]):
+                    if act[b, k] == object_plan.ABSENT:
+                        logit[b, k] = _ABSENT_LOGIT
+                    elif act[b, k] == object_plan.INJECT:
+                        m = torch.zeros_like(logit[b, k]) if labels is None else (lut[b][labels[b].to(torch.int64)] == k).to(logit.dtype)
+                        logit[b, k] = m * _NEW_OBJECT_SCALE - (-_ABSENT_LOGIT)
+        return logit, F.softmax(logit, dim=1)
+
     def _segment_core(self, frame, qry_rects, m_key, m_val, mem_rects, T, n_objects, K, batch_of_obj,
                       obj_begin=None, kv_rects=None):
         """Everything of ``segment`` after the box bookkeeping: query encoder, fused regional read,
