@@ -343,6 +343,51 @@ int rmnet_conv3x3_split_lds_f32(const float *x, const void *wpack, const float *
 int rmnet_conv3x3_rows_f32(const float *x, const void *wpack, const float *w_unscale, const float *bias, const float *res, int flags,
                            int N, int H, int W, int Cin, float *out, int32_t *range_word, void *stream);
 
+/* C1b gradients of the decoder convolutions (additive exports, same ABI version; csrc/conv3x3_wgrad.hip).
+ *
+ * The data gradient needs no entry of its own: for stride 1 / pad 1 it is rmnet_conv3x3_split_f32 on the gradient with the pack of
+ * the transposed, flipped weight (rmnet_amd.ops.conv3x3_dgrad_pack).  The weight and bias gradient is
+ *   dw[co][ky][kx][ci] = (sum over n, y, x of  g[n, y, x, co] * pre(x)[n, y + ky - 1, x + kx - 1, ci]) / (g_scale[0] * g_scale[1])
+ *   db[co]             = (sum over n, y, x of  g[n, y, x, co]) / (g_scale[0] * g_scale[1])
+ * with zeros outside the map and pre = ReLU under RMNET_CONV_RELU_IN (the only flag), in the three-term split-fp16 arithmetic of
+ * the forward with the pixel as reduction index.
+ *   x        [N, H, W, Cin] fp32 (channels-last), Cin % 32 == 0: the forward's input, split as the forward splits it (x 2^6, the
+ *            window |pre(x)| < 1023.5);
+ *   g        [N, H, W, 256] fp32: the gradient of the convolution's output AFTER staging, i.e. times the power of two
+ *            g_scale[0] * g_scale[1] that puts its largest element into [2^8, 2^9) (rmnet_conv_grad_stage_f32); it is split like x,
+ *            so |g| must be below 1023.5 as well;
+ *   g_scale  device pointer to two fp32 powers of two whose product is the staging scale; both are undone exactly when dw and db
+ *            are written ({1, 1} for a gradient that was not staged).  Nothing is read on the host;
+ *   dw       fp32, 9 * Cin * 256 elements in the channels-last strides of a [256, Cin, 3, 3] tensor: [co][ky][kx][ci];
+ *   db       fp32 [256], may be NULL;
+ *   workspace  rmnet_conv3x3_wgrad_workspace_bytes(N, H, W, Cin) bytes (0 for a shape the entry refuses): the pixel axis is cut into
+ *            ranges, each range's partial dw / db goes here and a merge kernel adds them in range order.  No atomics: every element
+ *            of dw and db is written exactly once and two calls return the same bits;
+ *   range_word  device int32, may be NULL: elements of pre(x) and of g outside the window (NaN / Inf included) are saturated and
+ *            added to it, once per element and call (the data gradient's calls of rmnet_conv3x3_split_f32 count g again, once
+ *            per call: a bad element of g is counted 1 + Cin / 256 times by a full backward).
+ * Every pointer 16-byte aligned (range_word: 4).  dw, db and the workspace must not overlap x, g, g_scale, range_word or each other.
+ * RMNET_E_INVALID_ARG for a NULL x, g, g_scale or dw, a non-positive size, another flag, a misaligned pointer or an overlap;
+ * RMNET_E_UNSUPPORTED for Cin % 32 != 0, W > 448 (the activation image of a pixel range and its halo of W + 1 pixels on either side
+ * must fit a CU's LDS) or N*H*W*max(Cin, 256) >= 2^31; RMNET_E_WORKSPACE for a NULL or short workspace -- all before anything is
+ * launched.  The kernel asks for more than 64 KB of dynamic LDS, which needs a function attribute: it is set at the first call on
+ * a device, and that first call must not come from a stream that is capturing (RMNET_E_UNSUPPORTED): call once eagerly before
+ * capturing. */
+size_t rmnet_conv3x3_wgrad_workspace_bytes(int N, int H, int W, int Cin);
+int rmnet_conv3x3_wgrad_f32(const float *x, const float *g, const float *g_scale, int flags, int N, int H, int W, int Cin, float *dw,
+                            float *db, void *workspace, size_t workspace_bytes, int32_t *range_word, void *stream);
+
+/* The stage pass in front of the two gradient GEMMs: one elementwise kernel, no host synchronisation.
+ *   gs[i] = (act == NULL || act[i] > 0 ? g[i] : 0) * 2^s        s = 9 - e for *amax in [2^(e-1), 2^e), so that 2^s *amax lies in
+ *   [2^8, 2^9); s = 0 when *amax is 0, NaN or Inf.  g_scale[0] * g_scale[1] = 2^s: g_scale[0] = 2^min(s, 126), g_scale[1] the rest
+ *   (1 unless *amax < 2^-118, where 2^s is no fp32 number).
+ * g, gs (and act) hold n floats, n % 4 == 0, 16-byte aligned; gs may be g itself.  *amax (device, 4-byte aligned) is an upper bound
+ * of |g[i]| taken before the mask; g_scale (device, 16-byte aligned) receives the two floats.  act is the forward's output under
+ * RMNET_CONV_RELU_OUT, else NULL.  RMNET_E_INVALID_ARG for a NULL g / amax / gs / g_scale, n < 1, n % 4 != 0, a misaligned pointer
+ * or an overlap other than gs == g; RMNET_E_UNSUPPORTED for n >= 2^31. */
+int rmnet_conv_grad_stage_f32(const float *g, const float *act, const float *amax, long long n, float *gs, float *g_scale,
+                              void *stream);
+
 /* C1 trunk / key-value convolutions (additive export, same ABI version): the arithmetic, range word and flags of
  * rmnet_conv3x3_split_f32 for kernel size ksize = 1 or 3 (padding ksize / 2), stride 1 or 2 and Cout % 64 == 0 (csrc/conv_split.hip).
  * Replaces the ResNet-50 bottleneck convolutions (BatchNorm folded into the pack, skip add and ReLU in the epilogue) and the two

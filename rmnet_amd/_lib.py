@@ -100,6 +100,11 @@ SIGNATURES = {
     'rmnet_conv3x3_rows_f32': (ctypes.c_int, [
         c_f32p, ctypes.c_void_p, c_f32p, c_f32p, c_f32p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
         c_f32p, c_i32p, ctypes.c_void_p]),
+    'rmnet_conv3x3_wgrad_workspace_bytes': (ctypes.c_size_t, [ctypes.c_int] * 4),
+    'rmnet_conv3x3_wgrad_f32': (ctypes.c_int, [
+        c_f32p, c_f32p, c_f32p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_f32p, c_f32p, ctypes.c_void_p,
+        ctypes.c_size_t, c_i32p, ctypes.c_void_p]),
+    'rmnet_conv_grad_stage_f32': (ctypes.c_int, [c_f32p, c_f32p, c_f32p, ctypes.c_longlong, c_f32p, c_f32p, ctypes.c_void_p]),
     'rmnet_conv_split_f32': (ctypes.c_int, [
         c_f32p, ctypes.c_void_p, c_f32p, c_f32p, c_f32p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
         ctypes.c_int, ctypes.c_int, ctypes.c_int, c_f32p, c_f32p, ctypes.c_int, c_i32p, ctypes.c_void_p]),

@@ -130,6 +130,12 @@ class ResBlock(nn.Module):
         r = self.conv2(F.relu(self.conv1(F.relu(x))))
         return (x if self.downsample is None else self.downsample(x)) + r
 
+    def _forward_grad(self, x):
+        """The block on the differentiable split-fp16 convolutions (``Decoder.device_grad_``): the two launches of the fused path,
+        each recorded with its backward.  The skip is read by conv2's epilogue and never written in place."""
+        t = _grad_conv(self, '1', self.conv1, x, relu_in=True, relu_out=True)
+        return _grad_conv(self, '2', self.conv2, t, res=x)
+
     def _forward_fused(self, x):
         """Same arithmetic: the convolutions run without bias and one pass adds the bias with the
         ReLU (conv1) or with the skip (conv2) -- 3 elementwise kernels instead of 5.  (Not always
@@ -245,6 +251,13 @@ class Refine(nn.Module):
         up = F.interpolate(pm, scale_factor=self.scale_factor, mode='bilinear', align_corners=False)
         return self.ResMM(s + up)
 
+    def _forward_grad(self, f, pm):
+        """``forward`` under ``Decoder.device_grad_``: the five convolutions differentiable on the device, the x2 upsample and the
+        add as plain torch ops."""
+        s = self.ResFS._forward_grad(_grad_conv(self, '', self.convFS, f))
+        up = F.interpolate(pm, scale_factor=self.scale_factor, mode='bilinear', align_corners=False)
+        return self.ResMM._forward_grad(s + up)
+
 
 class Decoder(nn.Module):
     """[mem | q_val] (1024 ch) + r3 + r2 -> 2-class logits at full resolution
@@ -258,7 +271,46 @@ class Decoder(nn.Module):
         self.RF2 = Refine(256, mdim)
         self.pred2 = nn.Conv2d(mdim, 2, 3, padding=1)
 
+    def device_grad_(self, enable=True):
+        """Opt in to (or out of) the decoder's gradient on the device.  With the flag set, a call that autograd has to record --
+        grad mode on and an input or a decoder parameter requiring grad -- runs the thirteen 256-output 3x3 convolutions through
+        the differentiable ``ops.conv3x3_split`` (forward: the split-fp16 kernels; backward: csrc/conv3x3_wgrad.hip and the same
+        forward kernel on flipped packs) in ``.train()`` and ``.eval()`` alike (the decoder holds no BatchNorm), provided the packs
+        are there (``fuse_epilogues()``), the run is channels-last CUDA fp32 and RMNET_CONV allows the decoder kernels.  The x2
+        upsample + add, ``pred2(relu(m2))`` and the x4 upsample are plain torch ops there.  A convolution's packs follow its
+        weight: they are rebuilt when ``weight._version`` has moved (an optimiser step) and cached otherwise -- on this path only:
+        before inference with weights that were updated in place, call ``fuse_epilogues()`` again, as ever.  Every other call takes
+        the path it took before.  Returns ``self``."""
+        for m in self.modules():
+            if isinstance(m, (Decoder, Refine, ResBlock)):
+                m._device_grad = bool(enable)
+        return self
+
+    def _grad_path_ok(self, r4, r3, r2):
+        if not getattr(self, '_device_grad', False) or not torch.is_grad_enabled():
+            return False
+        mods = [m for m in self.modules() if isinstance(m, (Decoder, Refine, ResBlock))]
+        if not all(getattr(m, '_fused', False) and getattr(m, '_conv_split', False) and getattr(m, '_device_grad', False) for m in mods):
+            return False
+        if any(isinstance(m, ResBlock) and m.downsample is not None for m in mods):
+            return False
+        cl = lambda t: t.is_contiguous(memory_format=torch.channels_last) and not t.is_contiguous()
+        for t, c in ((r4, self.convFM), (r3, self.RF3.convFS), (r2, self.RF2.convFS)):
+            if not (t.is_cuda and t.dtype == torch.float32 and t.dim() == 4 and t.shape[1] == c.in_channels and (cl(t) or cl(c.weight))):
+                return False
+        if split_conv_backend() not in ('full', 'split', 'trunk', 'decoder'):
+            return False
+        from . import ops
+        if max(r4.shape[3], r3.shape[3], r2.shape[3]) > ops.WGRAD_MAX_W:      # (the weight gradient's widest map: such inputs keep the old path)
+            return False
+        return any(t.requires_grad for t in (r4, r3, r2)) or any(p.requires_grad for p in self.parameters())
+
     def forward(self, r4, r3, r2):
+        if self._grad_path_ok(r4, r3, r2):
+            m4 = self.ResMM._forward_grad(_grad_conv(self, '', self.convFM, r4))
+            m2 = self.RF2._forward_grad(r2, self.RF3._forward_grad(r3, m4))
+            p2 = self.pred2(F.relu(m2))
+            return F.interpolate(p2.contiguous(), scale_factor=4, mode='bilinear', align_corners=False)
         if _split_conv_ok(self, r4, self.convFM):
             from . import ops
             r4 = r4.contiguous(memory_format=torch.channels_last)      # (the memory read's output is NCHW)
@@ -276,6 +328,39 @@ class Decoder(nn.Module):
         # (channels-last runs: back to NCHW HERE, on the 2-channel quarter-resolution map -- the decoder tail kernel reads NCHW planes, and
         #  converting after the x4 upsample would move 16x the bytes; a no-op for NCHW tensors)
         return F.interpolate(p2.contiguous(), scale_factor=4, mode='bilinear', align_corners=False)
+
+
+def _grad_packs(m, suffix, conv, need_x):
+    """(wpack, w_unscale, dgrad packs) of ``conv`` (packs ``m._wp<suffix>`` / ``m._wu<suffix>``) for the weight as it is now: the
+    forward pack is rebuilt when ``weight._version`` is not the version it was packed from, the dgrad packs (only when the input
+    needs a gradient: ``need_x``; Cin % 256 == 0: every decoder convolution) likewise; both are cached otherwise.  ``conv3x3_pack``
+    is device-side torch: no synchronisation."""
+    from . import ops
+    w = conv.weight
+    ver = w._version
+    if getattr(m, '_wver' + suffix, None) != ver:
+        with torch.no_grad():
+            wp, wu = ops.conv3x3_pack(w)
+        m._buffers['_wp' + suffix], m._buffers['_wu' + suffix] = wp, wu
+        setattr(m, '_wver' + suffix, ver)
+    if not need_x:
+        return getattr(m, '_wp' + suffix), getattr(m, '_wu' + suffix), None
+    cache = m.__dict__.setdefault('_dgrad_packs', {})
+    ent = cache.get(suffix)
+    if ent is None or ent[0] != ver or ent[1] is not w:
+        ent = cache[suffix] = (ver, w, ops.conv3x3_dgrad_pack(w))
+    return getattr(m, '_wp' + suffix), getattr(m, '_wu' + suffix), ent[2]
+
+
+def _grad_conv(m, suffix, conv, x, res=None, relu_in=False, relu_out=False):
+    """One decoder convolution on the differentiable ``ops.conv3x3_split`` with the packs of ``_grad_packs``."""
+    from . import ops
+    wp, wu, dp = _grad_packs(m, suffix, conv, x.requires_grad)
+    x = x.contiguous(memory_format=torch.channels_last)
+    if res is not None:
+        res = res.contiguous(memory_format=torch.channels_last)
+    return ops.conv3x3_split(x, wp, wu, conv.bias, res=res, relu_in=relu_in, relu_out=relu_out,
+                             range_word=ops.conv_range_word(x.device), weight=conv.weight, dgrad_packs=dp)
 
 
 # The stem and prediction-head kernels become part of the default path ('split') only on a measured win: per-step time in a kernel
@@ -609,6 +694,7 @@ def fuse_epilogues_(module, enable=True):
                     wp, wu, ok = None, None, False
                 put(m, '_wp' + suffix, wp)
                 put(m, '_wu' + suffix, wu)
+                setattr(m, '_wver' + suffix, c.weight._version)      # (Decoder.device_grad_: the packs follow the weight)
             if isinstance(m, Decoder):
                 # the prediction head (csrc/pred_head.hip) reads the plain fp32 weight: a flat NCHW copy, which .to(memory_format=...) leaves
                 put(m, '_wpred', m.pred2.weight.detach().contiguous().view(-1).clone() if m.pred2.weight.dtype == torch.float32 else None)

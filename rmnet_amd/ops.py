@@ -779,12 +779,26 @@ def conv3x3_rows_enabled():
     return v.strip() == '1'
 
 
-def conv3x3_split(x, wpack, w_unscale, bias=None, res=None, relu_in=False, relu_out=False, out=None, range_word=None):
+def conv3x3_split(x, wpack, w_unscale, bias=None, res=None, relu_in=False, relu_out=False, out=None, range_word=None, weight=None,
+                  dgrad_packs=None):
     """act(conv3x3(pre(x), w) + bias + res) for a channels-last fp32 ``x`` [N, Cin, H, W] and 256 output channels, stride 1,
     padding 1, on the split-fp16 MFMA kernel (csrc/conv3x3.hip); ``pre`` / ``act`` = ReLU when ``relu_in`` / ``relu_out``.
     ``wpack, w_unscale`` come from ``conv3x3_pack``.  ``out`` (channels-last, may be ``res``, must not be ``x``) defaults to a
     new tensor.  ``range_word`` (int32 [1] on the device): activations with |pre(x)| >= 1023.5, NaN or Inf are saturated
-    and counted there -- check it before trusting the result.  No fall-back: anything else is a RuntimeError."""
+    and counted there -- check it before trusting the result.  No fall-back: anything else is a RuntimeError.
+
+    Differentiable in ``x``, ``weight``, ``bias`` and ``res`` for a caller that passes ``weight`` (the [256, Cin, 3, 3] tensor the
+    pack was made from; the pack itself carries no gradient) or ``dgrad_packs``: when grad mode is on and one of the four requires
+    grad, the call is recorded as one ``torch.autograd.Function``.  The forward is the same launch; the backward stages the incoming gradient (``conv_grad_stage``), takes
+    the weight / bias gradient from ``conv3x3_wgrad`` and the data gradient from this kernel on ``dgrad_packs``
+    (``conv3x3_dgrad_pack(weight)``, built on the spot when not given; Cin % 256 == 0).  Only what ``needs_input_grad`` asks for is
+    computed, ``out`` must be left to the call, and there is no double backward.  Every other call takes the plain path: the bits
+    and the graph-free result of before."""
+    if (weight is not None or dgrad_packs is not None) and torch.is_grad_enabled() \
+            and any(isinstance(t, torch.Tensor) and t.requires_grad for t in (x, weight, bias, res)):
+        if out is not None:
+            raise RuntimeError('conv3x3_split under autograd allocates its own output: out must be None')
+        return _Conv3x3SplitFn.apply(x, weight, bias, res, wpack, w_unscale, dgrad_packs, bool(relu_in), bool(relu_out), range_word)
     _check_act(x, 'x')
     if x.dim() != 4 or not x.is_contiguous(memory_format=torch.channels_last):
         raise RuntimeError('x must be a channels-last [N, Cin, H, W] tensor')
@@ -829,6 +843,190 @@ def conv3x3_split(x, wpack, w_unscale, bias=None, res=None, relu_in=False, relu_
                                  _ptr(out), _ptr(range_word), _stream(x.device))
     _lib.check(rc, entry)
     return out
+
+
+# ---- gradients of conv3x3_split (csrc/conv3x3_wgrad.hip) ------------------------------------------------------------------------
+# The weight-gradient kernel's constants, restated by tests/test_conv_grad.py: input channels per workgroup, pixels per K step,
+# pixels per activation image (a range longer than that is walked in several images), the widest map, and the range plan's three.
+WGRAD_CT, WGRAD_KT, WGRAD_SUB, WGRAD_MAX_W = 16, 32, 512, 448
+WGRAD_RANGE_MIN, WGRAD_MAX_RANGES, WGRAD_TARGET_WGS = 256, 64, 768
+WGRAD_BIAS_SPLIT = 8              # the bias gradient sums a range in that many chunks
+GRAD_TOP_EXP = 9                  # a staged gradient's largest element lies in [2^8, 2^9)
+
+# Launches made by the gradient path, counted on the Python side ('pack' counts conv3x3_dgrad_pack calls); tests reset and read it.
+conv_grad_launches = {'stage': 0, 'wgrad': 0, 'dgrad': 0, 'pack': 0}
+
+
+def conv3x3_wgrad_plan(pixels, cin):
+    """(channel tiles, ranges, pixels per range) of ``conv3x3_wgrad`` for N*H*W = ``pixels``: csrc/conv3x3_wgrad.hip, wgrad_plan."""
+    nct = cin // WGRAD_CT
+    nr = max(1, min(WGRAD_TARGET_WGS // nct, -(-pixels // WGRAD_RANGE_MIN), WGRAD_MAX_RANGES))
+    rl = -(-(-(-pixels // nr)) // WGRAD_KT) * WGRAD_KT
+    return nct, -(-pixels // rl), rl
+
+
+_grad_range_words = {}
+
+
+def conv_grad_range_word(device):
+    """The device's int32 range word of the convolutions' BACKWARD (created on first use: call it once outside graph capture):
+    staged gradients and saved activations outside the fp16 window, NaN and Inf are counted here, never in ``conv_range_word``,
+    which stays what the forward left in it."""
+    idx = torch.device(device).index
+    idx = torch.cuda.current_device() if idx is None else idx
+    w = _grad_range_words.get(idx)
+    if w is None:
+        w = _grad_range_words[idx] = torch.zeros(1, dtype=torch.int32, device=torch.device('cuda', idx))
+    return w
+
+
+@torch.no_grad()
+def conv3x3_dgrad_pack(weight):
+    """The packs of the data gradient of a [256, Cin, 3, 3] convolution, Cin % 256 == 0: for stride 1 / pad 1,
+    dX = conv3x3(G, W transposed and flipped), a convolution with 256 inputs and Cin outputs, i.e. Cin / 256 calls of
+    ``conv3x3_split``.  Returns the list of ``conv3x3_pack(weight.transpose(0, 1).flip(2, 3)[256 s : 256 (s + 1)])``."""
+    if weight.dim() != 4 or weight.shape[0] != CONV_COUT or tuple(weight.shape[2:]) != (3, 3) or weight.shape[1] % CONV_COUT:
+        raise RuntimeError('conv3x3_dgrad_pack needs a [256, Cin, 3, 3] weight with Cin %% 256 == 0, got %s' % (tuple(weight.shape),))
+    conv_grad_launches['pack'] += 1
+    wt = weight.detach().transpose(0, 1).flip(2, 3)
+    return [conv3x3_pack(wt[s * CONV_COUT:(s + 1) * CONV_COUT]) for s in range(weight.shape[1] // CONV_COUT)]
+
+
+def conv_grad_stage_exponent(amax):
+    """s (an int32 tensor like ``amax``, any device) with 2^s * amax in [2^8, 2^9): 9 - e for amax in [2^(e-1), 2^e), subnormals
+    included; 0 for amax = 0, NaN or Inf.  What csrc/conv3x3_wgrad.hip: conv_grad_stage computes on the device."""
+    a = amax.detach().to(torch.float32)
+    _, ex = torch.frexp(a)
+    return torch.where((a > 0) & torch.isfinite(a), GRAD_TOP_EXP - ex, torch.zeros_like(ex))
+
+
+def conv_grad_stage(g, act=None, amax=None, out=None):
+    """The stage pass of a convolution's backward, one kernel and no host synchronisation: ``gs = [act > 0] * g * 2^s`` with
+    ``s = conv_grad_stage_exponent(amax)``.  ``g`` (fp32, dense; ``act`` of the same shape and strides, or None) is the incoming
+    gradient, ``amax`` a 0-dim fp32 upper bound of |g| on the device, taken before the mask (default: the largest |element|, one
+    reduction).  Returns ``(gs, g_scale)``: ``gs`` like ``g`` (``out`` may be ``g`` itself) and ``g_scale`` fp32 [2], two powers
+    of two whose product is 2^s (the second is 1 unless amax < 2^-118)."""
+    _check_act(g, 'g')
+    if amax is None:
+        amax = torch.linalg.vector_norm(g, float('inf'))
+    _check(amax, 'amax')
+    if amax.numel() != 1:
+        raise RuntimeError('amax must hold one element')
+    if act is not None:
+        _check_act(act, 'act')
+        if act.shape != g.shape or act.stride() != g.stride():
+            raise RuntimeError('act must have the shape and strides of g')
+    if g.numel() == 0 or g.numel() % 4:
+        raise RuntimeError('conv_grad_stage needs a non-empty g with a multiple of 4 elements')
+    gs = torch.empty_like(g) if out is None else out
+    if gs.shape != g.shape or gs.stride() != g.stride() or gs.dtype != g.dtype:
+        raise RuntimeError('out must have the shape, strides and dtype of g')
+    g_scale = torch.empty(4, dtype=torch.float32, device=g.device)[:2]
+    for t in (act, amax, gs):
+        if t is not None and t.device != g.device:
+            raise RuntimeError('conv_grad_stage: every tensor must be on %s' % g.device)
+    lib = _lib.load()
+    with torch.cuda.device(g.device):
+        rc = lib.rmnet_conv_grad_stage_f32(_ptr(g), _ptr(act), _ptr(amax), g.numel(), _ptr(gs), _ptr(g_scale), _stream(g.device))
+    _lib.check(rc, 'rmnet_conv_grad_stage_f32')
+    conv_grad_launches['stage'] += 1
+    return gs, g_scale
+
+
+def conv3x3_wgrad(x, g, g_scale, relu_in=False, want_bias=True, range_word=None):
+    """The weight and bias gradient of ``conv3x3_split`` (csrc/conv3x3_wgrad.hip, include/rmnet_hip.h: rmnet_conv3x3_wgrad_f32):
+    ``dW[co, ci, ky, kx] = sum g[n, co, y, x] * pre(x)[n, ci, y + ky - 1, x + kx - 1] / (g_scale[0] * g_scale[1])`` and
+    ``db[co] = sum g[n, co, y, x] / (g_scale[0] * g_scale[1])`` for channels-last fp32 ``x`` [N, Cin, H, W] (the forward's input,
+    ``pre`` = ReLU under ``relu_in``) and ``g`` [N, 256, H, W] (the STAGED gradient of ``conv_grad_stage`` with its ``g_scale``;
+    ``torch.ones(2)`` for a gradient that is already inside |g| < 1023.5).  Returns ``(dW, db)``: dW a channels-last
+    [256, Cin, 3, 3] tensor, db [256] or None.  Deterministic: no atomics, the same bits on every call.  ``range_word``: the
+    backward's (``conv_grad_range_word``)."""
+    for t, n in ((x, 'x'), (g, 'g')):
+        _check_act(t, n)
+        if t.dim() != 4 or not t.is_contiguous(memory_format=torch.channels_last):
+            raise RuntimeError('%s must be a channels-last 4-D tensor' % n)
+    N, cin, H, W = x.shape
+    if tuple(g.shape) != (N, CONV_COUT, H, W):
+        raise RuntimeError('g must be [N, 256, H, W] for x [N, Cin, H, W], got %s and %s' % (tuple(g.shape), tuple(x.shape)))
+    if cin % 32:
+        raise RuntimeError('conv3x3_wgrad needs Cin % 32 == 0, got %d' % cin)
+    _check(g_scale, 'g_scale')
+    if g_scale.numel() != 2:
+        raise RuntimeError('g_scale must hold two floats')
+    if range_word is not None:
+        _check(range_word, 'range_word', torch.int32)
+    for t in (g, g_scale, range_word):
+        if t is not None and t.device != x.device:
+            raise RuntimeError('conv3x3_wgrad: every tensor must be on %s' % x.device)
+    dw = torch.empty((CONV_COUT, cin, 3, 3), dtype=torch.float32, device=x.device, memory_format=torch.channels_last)
+    db = torch.empty(CONV_COUT, dtype=torch.float32, device=x.device) if want_bias else None
+    lib = _lib.load()
+    nbytes = lib.rmnet_conv3x3_wgrad_workspace_bytes(N, H, W, cin)
+    ws = _ws(nbytes, x.device)
+    with torch.cuda.device(x.device):
+        rc = lib.rmnet_conv3x3_wgrad_f32(_ptr(x), _ptr(g), _ptr(g_scale), CONV_RELU_IN if relu_in else 0, N, H, W, cin, _ptr(dw),
+                                         _ptr(db), _ptr(ws), ws.numel(), _ptr(range_word), _stream(x.device))
+    _lib.check(rc, 'rmnet_conv3x3_wgrad_f32')
+    conv_grad_launches['wgrad'] += 1
+    return dw, db
+
+
+def conv3x3_dgrad(gs, g_scale, dgrad_packs, range_word=None):
+    """The data gradient of ``conv3x3_split`` from the staged gradient ``gs`` [N, 256, H, W] (``conv_grad_stage``): one
+    ``conv3x3_split`` per 256 input channels on the packs of ``conv3x3_dgrad_pack``, with ``w_unscale / (g_scale[0] * g_scale[1])``
+    in place of ``w_unscale`` (exact: powers of two); the slices are concatenated in channels-last.  No mask is applied here."""
+    inv = g_scale.reciprocal()
+    parts = []
+    for wp, wu in dgrad_packs:
+        parts.append(conv3x3_split(gs, wp, wu * inv[0] * inv[1], range_word=range_word))
+        conv_grad_launches['dgrad'] += 1
+    return parts[0] if len(parts) == 1 else torch.cat(parts, dim=1)
+
+
+class _Conv3x3SplitFn(torch.autograd.Function):
+    """conv3x3_split under autograd: out = act(conv(pre(x)) + bias + res).  Saves x and, under relu_out, out -- nothing else."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, res, wpack, w_unscale, dgrad_packs, relu_in, relu_out, range_word):
+        det = lambda t: None if t is None else t.detach()
+        out = conv3x3_split(det(x), wpack, w_unscale, det(bias), det(res), relu_in, relu_out, range_word=range_word)
+        need_x = ctx.needs_input_grad[0]
+        if need_x and dgrad_packs is None and weight is None:
+            raise RuntimeError('conv3x3_split: the gradient with respect to x needs weight or dgrad_packs')
+        if need_x and x.shape[1] % CONV_COUT:
+            raise RuntimeError('conv3x3_split: the gradient with respect to x needs Cin %% 256 == 0, got %d' % x.shape[1])
+        if weight is not None and weight.requires_grad and tuple(weight.shape) != (CONV_COUT, x.shape[1], 3, 3):
+            raise RuntimeError('weight must be [256, Cin, 3, 3]')
+        # (the packs are made from the weight as it is NOW: an optimiser step between forward and backward must not change the gradient)
+        ctx.dgrad_packs = (dgrad_packs if dgrad_packs is not None else conv3x3_dgrad_pack(weight)) if need_x else None
+        ctx.relu_in, ctx.relu_out = relu_in, relu_out
+        ctx.save_for_backward(x, *((out,) if relu_out else ()))
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        saved = ctx.saved_tensors
+        x = saved[0].detach()
+        out = saved[1] if ctx.relu_out else None
+        need_x, need_w, need_b, need_r = ctx.needs_input_grad[:4]
+        g = grad_out.contiguous(memory_format=torch.channels_last)          # (an expanded or NCHW grad_output becomes a plain tensor)
+        gx = gw = gb = gr = None
+        if need_r:
+            gr = g if out is None else torch.ops.aten.threshold_backward(g, out, 0)
+        if need_x or need_w:
+            grw = conv_grad_range_word(x.device)
+            gs, g_scale = conv_grad_stage(g, out)
+            if need_w:
+                gw, gb = conv3x3_wgrad(x, gs, g_scale, ctx.relu_in, want_bias=need_b, range_word=grw)
+            if need_x:
+                gx = conv3x3_dgrad(gs, g_scale, ctx.dgrad_packs, range_word=grw)
+                if ctx.relu_in:
+                    gx = torch.ops.aten.threshold_backward(gx, x, 0)
+        if need_b and gb is None:                                           # (a trainable bias on frozen weights: no GEMM)
+            gm = g if out is None else (gr if gr is not None else torch.ops.aten.threshold_backward(g, out, 0))
+            gb = gm.sum(dim=(0, 2, 3))
+        return gx, gw, gb, gr, None, None, None, None, None, None
 
 
 @torch.no_grad()
