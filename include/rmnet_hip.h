@@ -885,6 +885,47 @@ int rmnet_clip_loss_grad_f32(const float *probs, const uint8_t *labels, int N, i
                              float *grad, double *per_class, double *nll_sum, long long *counts, void *workspace,
                              size_t workspace_bytes, void *stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * J1  Adjoint of the bilinear upsample by 2 or 4, align_corners = False (additive exports, same ABI version;
+ *     csrc/decoder_glue_bwd.hip).
+ * Replaces: the backward of F.interpolate(x, scale_factor=S, mode='bilinear', align_corners=False) (models/rmnet.py:117-119, 139),
+ *           which scatters with floating-point atomic adds on the GPU.
+ *   g    [N,C,S h,S w] float32, the gradient of the fine map;  out [N,C,h,w] float32, every element written exactly once.
+ *        nhwc != 0: both are [N,.,.,C] in memory, C % 4 == 0, both 16-byte aligned; otherwise NCHW, 4-byte aligned (fine rows are
+ *        read 16 bytes at a time when g is 16-byte aligned and S w % 4 == 0).  out must not overlap g.
+ *   With the forward's rule src = max((d + 0.5) / S - 0.5, 0), i0 = floor(src), i1 = i0 + (i0 < n - 1), coarse j of an axis of length n
+ *   reads the fine indices S j - S/2 + t, t = 0 .. 2 S - 1, with the weights (2 t + 1) / (2 S) for t < S and their mirror image behind;
+ *   at j = 0 the first S/2 taps do not exist and the next S/2 weigh 1; at j = n - 1 the mirror image of that.  2-D is the outer
+ *   product.  Order of one element: fine rows ascending; in a row s = fma(wx, g, s) over the existing fine columns ascending from
+ *   s = 0, then acc = fma(wy, s, acc).  No atomics: the same bits from call to call.
+ * RMNET_E_INVALID_ARG for a NULL or misaligned pointer, a non-positive size, C % 4 under nhwc or overlapping buffers;
+ * RMNET_E_UNSUPPORTED for any other factor or >= 2^31 elements of g.  Nothing is launched then.
+ * ------------------------------------------------------------------------------------------- */
+int rmnet_upsample_bwd_f32(const float *g, long long N, int C, int h, int w, int factor, int nhwc, float *out, void *stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * J2  Backward of the prediction head (rmnet_pred_head_f32), out = conv3x3_p1(relu(x), w) + bias (additive exports; csrc/decoder_glue_bwd.hip).
+ * Replaces: the backward of self.pred2(F.relu(m2)) (models/rmnet.py:138): threshold_backward, the library's two convolution
+ *           gradients and the layout copies between them.
+ *   x  [n,Hq,Wq,C] float32 channels-last, C % 32 == 0, 16-byte aligned;  w [2][C][3][3], 16-byte aligned;  g [n,2,Hq,Wq] NCHW.
+ *   With G[k][ky][kx](y, x) = g[k][y - ky + 1][x - kx + 1], zero outside the map:
+ *   dx [n,Hq,Wq,C] channels-last, 16-byte aligned:  [x > 0] * sum over k, ky, kx (that order, fma from 0) of w[k][c][ky][kx] * G;
+ *                  a NaN in x gives 0 (threshold_backward's rule).
+ *   dw [2][C][3][3]:  sum over the pixels of relu(x)[p][c] * G[k][ky][kx](p), relu(x) = x > 0 ? x : 0 (a NaN counts as 0).
+ *   db [2]:           sum over the pixels of g[k][p].
+ *   Any of dx, dw, db may be NULL: that part is skipped (all three: nothing is launched, RMNET_OK).  dw and db are summed per pixel
+ *   range (32 slots of every 32nd pixel, added in slot order) into the workspace and merged in range order by a second kernel: no
+ *   atomics, every element written once, the same bits from call to call.
+ *   workspace  16-byte aligned, at least rmnet_pred_head_bwd_workspace_bytes(n, Hq, Wq, C) bytes (0 for a shape that is refused);
+ *              only read when dw or db is asked for.
+ * RMNET_E_INVALID_ARG for a NULL x / w / g, a non-positive size, a misaligned pointer, or an output that overlaps an input or
+ * another output; RMNET_E_UNSUPPORTED for C % 32 != 0 or n Hq Wq C >= 2^31; RMNET_E_WORKSPACE for a NULL or short workspace when dw
+ * or db is asked for.  Nothing is launched then.
+ * ------------------------------------------------------------------------------------------- */
+size_t rmnet_pred_head_bwd_workspace_bytes(int n, int Hq, int Wq, int C);
+int rmnet_pred_head_bwd_f32(const float *x, const float *w, const float *g, int n, int Hq, int Wq, int C, float *dx, float *dw,
+                            float *db, void *workspace, size_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

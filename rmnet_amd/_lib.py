@@ -182,6 +182,12 @@ SIGNATURES = {
     'rmnet_clip_loss_grad_f32': (ctypes.c_int, [
         c_f32p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_f32p,
         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
+    'rmnet_upsample_bwd_f32': (ctypes.c_int, [
+        c_f32p, ctypes.c_longlong, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_f32p, ctypes.c_void_p]),
+    'rmnet_pred_head_bwd_workspace_bytes': (ctypes.c_size_t, [ctypes.c_int] * 4),
+    'rmnet_pred_head_bwd_f32': (ctypes.c_int, [
+        c_f32p, c_f32p, c_f32p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_f32p, c_f32p, c_f32p, ctypes.c_void_p,
+        ctypes.c_size_t, ctypes.c_void_p]),
 }
 
 ABI_VERSION = 6

@@ -252,9 +252,13 @@ class Refine(nn.Module):
         return self.ResMM(s + up)
 
     def _forward_grad(self, f, pm):
-        """``forward`` under ``Decoder.device_grad_``: the five convolutions differentiable on the device, the x2 upsample and the
-        add as plain torch ops."""
+        """``forward`` under ``Decoder.device_grad_``: the five convolutions differentiable on the device; the x2 upsample and the
+        add as plain torch ops, or, with ``glue=True`` and ``scale_factor == 2``, as the recorded ``ops.upsample2x_add`` (one launch
+        forward, a gather backward)."""
         s = self.ResFS._forward_grad(_grad_conv(self, '', self.convFS, f))
+        if getattr(self, '_glue_grad', False) and self.scale_factor == 2:
+            from . import ops
+            return self.ResMM._forward_grad(ops.upsample2x_add(pm, s))
         up = F.interpolate(pm, scale_factor=self.scale_factor, mode='bilinear', align_corners=False)
         return self.ResMM._forward_grad(s + up)
 
@@ -271,19 +275,25 @@ class Decoder(nn.Module):
         self.RF2 = Refine(256, mdim)
         self.pred2 = nn.Conv2d(mdim, 2, 3, padding=1)
 
-    def device_grad_(self, enable=True):
+    def device_grad_(self, enable=True, glue=False):
         """Opt in to (or out of) the decoder's gradient on the device.  With the flag set, a call that autograd has to record --
         grad mode on and an input or a decoder parameter requiring grad -- runs the thirteen 256-output 3x3 convolutions through
         the differentiable ``ops.conv3x3_split`` (forward: the split-fp16 kernels; backward: csrc/conv3x3_wgrad.hip and the same
         forward kernel on flipped packs) in ``.train()`` and ``.eval()`` alike (the decoder holds no BatchNorm), provided the packs
         are there (``fuse_epilogues()``), the run is channels-last CUDA fp32 and RMNET_CONV allows the decoder kernels.  The x2
-        upsample + add, ``pred2(relu(m2))`` and the x4 upsample are plain torch ops there.  A convolution's packs follow its
+        upsample + add, ``pred2(relu(m2))`` and the x4 upsample are plain torch ops there, unless ``glue=True``: then they are the
+        recorded ``ops.upsample2x_add`` (both ``Refine`` modules with ``scale_factor == 2``), ``ops.pred_head`` on the LIVE
+        ``pred2.weight`` (a biased 3x3 / stride 1 / pad 1 convolution with two outputs and Cin % 32 == 0; any other ``pred2`` stays
+        torch's) and ``ops.upsample4x``, whose backwards are the gathers and the one-pass kernel of csrc/decoder_glue_bwd.hip: the
+        decoder is then differentiable on the device end to end, without an atomic add, and two ``backward()`` calls give the same
+        bits in every gradient.  ``device_grad_()`` without the flag is what it was.  A convolution's packs follow its
         weight: they are rebuilt when ``weight._version`` has moved (an optimiser step) and cached otherwise -- on this path only:
         before inference with weights that were updated in place, call ``fuse_epilogues()`` again, as ever.  Every other call takes
         the path it took before.  Returns ``self``."""
         for m in self.modules():
             if isinstance(m, (Decoder, Refine, ResBlock)):
                 m._device_grad = bool(enable)
+                m._glue_grad = bool(enable) and bool(glue)
         return self
 
     def _grad_path_ok(self, r4, r3, r2):
@@ -309,6 +319,15 @@ class Decoder(nn.Module):
         if self._grad_path_ok(r4, r3, r2):
             m4 = self.ResMM._forward_grad(_grad_conv(self, '', self.convFM, r4))
             m2 = self.RF2._forward_grad(r2, self.RF3._forward_grad(r3, m4))
+            if getattr(self, '_glue_grad', False):
+                from . import ops
+                if _pred_head_shape_ok(self.pred2) and self.pred2.weight.dtype == torch.float32:
+                    # (the live weight, not the _wpred copy, which an optimiser step leaves stale; its gradient comes back as a plain
+                    #  [2, C, 3, 3] tensor and autograd carries it through contiguous() to the channels-last parameter)
+                    p2 = ops.pred_head(m2.contiguous(memory_format=torch.channels_last), self.pred2.weight.contiguous(), self.pred2.bias)
+                else:
+                    p2 = self.pred2(F.relu(m2)).contiguous()
+                return ops.upsample4x(p2)
             p2 = self.pred2(F.relu(m2))
             return F.interpolate(p2.contiguous(), scale_factor=4, mode='bilinear', align_corners=False)
         if _split_conv_ok(self, r4, self.convFM):
@@ -432,13 +451,18 @@ def _split_conv_ok(m, x, conv):
     return conv.out_channels == 256 and conv.in_channels % 32 == 0 and _split_path_ok(m, x, conv, ('full', 'split', 'trunk', 'decoder'))
 
 
+def _pred_head_shape_ok(c):
+    """``c`` is a convolution the prediction-head kernels implement: 3x3 / stride 1 / pad 1, two biased outputs, Cin % 32 == 0."""
+    if c.bias is None or c.out_channels != 2 or c.in_channels % 32:
+        return False
+    return c.kernel_size == (3, 3) and c.stride == (1, 1) and c.padding == (1, 1) and c.dilation == (1, 1) and c.groups == 1
+
+
 def _pred_head_ok(m, x):
     """The prediction-head kernel (csrc/pred_head.hip) serves ``m.pred2`` of Decoder ``m`` on input ``x``: ``_split_path_ok`` under
     RMNET_CONV=full (and =split once HEAD_DEFAULT is set), a flat copy of the weight present, 3x3 / stride 1 / pad 1, two biased outputs, Cin % 32 == 0."""
     c = m.pred2
-    if getattr(m, '_wpred', None) is None or c.bias is None or c.out_channels != 2 or c.in_channels % 32:
-        return False
-    if c.kernel_size != (3, 3) or c.stride != (1, 1) or c.padding != (1, 1) or c.dilation != (1, 1) or c.groups != 1:
+    if getattr(m, '_wpred', None) is None or not _pred_head_shape_ok(c):
         return False
     return _split_path_ok(m, x, c, ('full', 'split') if HEAD_DEFAULT else ('full',))
 

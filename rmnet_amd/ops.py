@@ -12,6 +12,7 @@ import os
 
 import numpy as np
 import torch
+import torch.nn.functional as F
 
 from . import _lib
 
@@ -556,7 +557,16 @@ def upsample2x_add(x, skip=None, out=None):
     The kernel is chosen by the operands: channels-last if ``x`` or ``skip`` is (the other one is converted), NCHW otherwise, and
     the result has that memory format.  An NCHW ``out`` next to channels-last operands is NOT written: a new channels-last tensor
     is returned instead (networks.Refine passes out=s whatever the layouts are and uses the returned value).  The other mismatch,
-    a channels-last ``out`` next to NCHW operands, raises: the NCHW kernel would fill its storage in the wrong order."""
+    a channels-last ``out`` next to NCHW operands, raises: the NCHW kernel would fill its storage in the wrong order.
+
+    Differentiable in ``x`` and ``skip``: when grad mode is on and one of them requires grad, the call is recorded as one
+    ``torch.autograd.Function`` that saves nothing.  The forward is the same launch into a new tensor (``out`` must be None); the
+    backward hands the incoming gradient to ``skip`` as it is and ``upsample_backward(g, 2)`` to ``x``.  No double backward.
+    Every other call takes the plain path."""
+    if torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad for t in (x, skip)):
+        if out is not None:
+            raise RuntimeError('upsample2x_add under autograd allocates its own output: out must be None')
+        return _Upsample2xAddFn.apply(x, skip)
     _check_act(x, 'x')
     if x.dim() != 4:
         raise RuntimeError('x must be [N,C,h,w]')
@@ -589,6 +599,156 @@ def upsample2x_add(x, skip=None, out=None):
         rc = lib.rmnet_upsample2x_add_f32(_ptr(x), _ptr(skip), N, C, h, w, _ptr(out), _stream(x.device))
     _lib.check(rc, 'rmnet_upsample2x_add_f32')
     return out
+
+
+# ---- gradients of the decoder's glue (csrc/decoder_glue_bwd.hip) ----------------------------------------------------------------
+# The kernels' constants, restated by tests/test_decoder_glue_grad.py: threads per workgroup, the upsample adjoint's largest grid,
+# and the prediction head's channels per workgroup, pixel slots and range plan.
+GLUE_THREADS, UPSAMPLE_BWD_MAX_BLOCKS = 256, 1024
+PRED_BWD_CT, PRED_BWD_SLOTS = 32, 32
+PRED_BWD_RANGE_MIN, PRED_BWD_MAX_RANGES, PRED_BWD_TARGET_WGS = 256, 128, 1024
+
+
+def pred_head_backward_plan(pixels, C):
+    """(channel tiles, ranges, pixels per range) of ``pred_head_backward`` for n*Hq*Wq = ``pixels``: csrc/decoder_glue_bwd.hip, ph_plan."""
+    nct = C // PRED_BWD_CT
+    nr = max(1, min(PRED_BWD_TARGET_WGS // nct, -(-pixels // PRED_BWD_RANGE_MIN), PRED_BWD_MAX_RANGES))
+    rl = -(-(-(-pixels // nr)) // PRED_BWD_SLOTS) * PRED_BWD_SLOTS
+    return nct, -(-pixels // rl), rl
+
+
+def upsample_backward(g, factor, out=None):
+    """The adjoint of ``F.interpolate(x, scale_factor=factor, mode='bilinear', align_corners=False)`` for ``factor`` 2 or 4
+    (csrc/decoder_glue_bwd.hip, include/rmnet_hip.h: rmnet_upsample_bwd_f32): ``g`` [N,C,factor*h,factor*w] fp32, the gradient of
+    the fine map, -> the gradient [N,C,h,w] of the coarse one.  Channels-last if ``g`` is (C % 4 == 0), NCHW otherwise, and the
+    result (``out``, when given, must have it) has that memory format.  A gather with constant weights: no atomics, every element
+    written once, the same bits on every call.  No fall-back: anything else is a RuntimeError."""
+    _check_act(g, 'g')
+    factor = int(factor)
+    if factor not in (2, 4):
+        raise RuntimeError('upsample_backward serves factor 2 and 4, got %d' % factor)
+    if g.dim() != 4 or g.shape[2] % factor or g.shape[3] % factor or g.numel() == 0:
+        raise RuntimeError('g must be a non-empty [N,C,%d h,%d w] tensor, got %s' % (factor, factor, tuple(g.shape)))
+    N, C, H, W = g.shape
+    h, w = H // factor, W // factor
+    cl = _is_cl(g)
+    if cl and C % 4:
+        raise RuntimeError('a channels-last g needs C %% 4 == 0, got %d' % C)
+    shape = (N, C, h, w)
+    if out is None:
+        out = torch.empty(shape, dtype=g.dtype, device=g.device, memory_format=torch.channels_last if cl else torch.contiguous_format)
+    else:
+        _check_act(out, 'out')
+        if tuple(out.shape) != shape or out.device != g.device:
+            raise RuntimeError('out must be [N,C,h,w] on the device of g')
+        if not out.is_contiguous(memory_format=torch.channels_last if cl else torch.contiguous_format):
+            raise RuntimeError('out must have the memory format of g')
+    lib = _lib.load()
+    with torch.cuda.device(g.device):
+        rc = lib.rmnet_upsample_bwd_f32(_ptr(g), N, C, h, w, factor, 1 if cl else 0, _ptr(out), _stream(g.device))
+    _lib.check(rc, 'rmnet_upsample_bwd_f32')
+    return out
+
+
+def _glue_grad_input(g):
+    """An incoming gradient as a tensor ``upsample_backward`` takes: itself when dense (NCHW, or channels-last with C % 4 == 0),
+    else an NCHW copy (an expanded or sliced grad_output)."""
+    if g.is_contiguous() or (_is_cl(g) and g.shape[1] % 4 == 0):
+        return g
+    return g.contiguous()
+
+
+class _Upsample2xAddFn(torch.autograd.Function):
+    """upsample2x_add under autograd.  Saves nothing: both maps are linear."""
+
+    @staticmethod
+    def forward(ctx, x, skip):
+        ctx.set_materialize_grads(False)
+        return upsample2x_add(x.detach(), None if skip is None else skip.detach())
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        if g is None:
+            return None, None
+        gx = upsample_backward(_glue_grad_input(g), 2) if ctx.needs_input_grad[0] else None
+        return gx, (g if ctx.needs_input_grad[1] else None)
+
+
+class _Upsample4xFn(torch.autograd.Function):
+    """upsample4x under autograd: torch's forward, the gather of upsample_backward instead of torch's atomic scatter behind it."""
+
+    @staticmethod
+    def forward(ctx, x):
+        ctx.set_materialize_grads(False)
+        return F.interpolate(x.detach(), scale_factor=4, mode='bilinear', align_corners=False)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        return None if g is None else upsample_backward(g.contiguous(), 4)
+
+
+def upsample4x(x):
+    """``F.interpolate(x, scale_factor=4, mode='bilinear', align_corners=False)``: the decoder's last step.  The forward is that
+    call; on a CUDA fp32 ``x`` that requires grad (grad mode on) it is recorded as one ``torch.autograd.Function`` whose backward is
+    ``upsample_backward(g.contiguous(), 4)`` -- deterministic, where torch's own backward adds with atomics.  No double backward.
+    On the CPU, and for every call that needs no gradient, it is the plain torch op."""
+    if isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and x.requires_grad and torch.is_grad_enabled():
+        return _Upsample4xFn.apply(x)
+    return F.interpolate(x, scale_factor=4, mode='bilinear', align_corners=False)
+
+
+def pred_head_backward(x, weight, g, need=(True, True, True)):
+    """The gradients of ``pred_head`` (csrc/decoder_glue_bwd.hip, include/rmnet_hip.h: rmnet_pred_head_bwd_f32) for a channels-last
+    fp32 ``x`` [n, C, Hq, Wq] (the forward's input, C % 32 == 0), ``weight`` [2, C, 3, 3] and the NCHW-contiguous gradient ``g``
+    [n, 2, Hq, Wq] of the output.  Returns ``(dx, dw, db)`` -- dx channels-last like x, masked by ``x > 0`` (a NaN in x: 0), dw
+    [2, C, 3, 3], db [2] -- with None for the parts ``need`` does not ask for.  One pass over x, per-range partials merged in range
+    order: no atomics, the same bits on every call.  No fall-back: anything else is a RuntimeError."""
+    _check_act(x, 'x')
+    if x.dim() != 4 or not x.is_contiguous(memory_format=torch.channels_last) or x.numel() == 0:
+        raise RuntimeError('x must be a non-empty channels-last [n, C, Hq, Wq] tensor')
+    n, C, H, W = x.shape
+    if C % 32:
+        raise RuntimeError('pred_head_backward needs C %% 32 == 0, got %d' % C)
+    _check(weight, 'weight')
+    _check(g, 'g')
+    if tuple(weight.shape) != (2, C, 3, 3) or tuple(g.shape) != (n, 2, H, W):
+        raise RuntimeError('pred_head_backward needs weight [2, %d, 3, 3] and g [%d, 2, %d, %d], got %s / %s'
+                           % (C, n, H, W, tuple(weight.shape), tuple(g.shape)))
+    if weight.device != x.device or g.device != x.device:
+        raise RuntimeError('pred_head_backward: every tensor must be on %s' % x.device)
+    need_x, need_w, need_b = (bool(v) for v in need)
+    dx = torch.empty(x.shape, dtype=x.dtype, device=x.device, memory_format=torch.channels_last) if need_x else None
+    dw = torch.empty((2, C, 3, 3), dtype=x.dtype, device=x.device) if need_w else None
+    db = torch.empty(2, dtype=x.dtype, device=x.device) if need_b else None
+    if not (need_x or need_w or need_b):
+        return dx, dw, db
+    lib = _lib.load()
+    ws = _ws(lib.rmnet_pred_head_bwd_workspace_bytes(n, H, W, C), x.device) if need_w or need_b else None
+    with torch.cuda.device(x.device):
+        rc = lib.rmnet_pred_head_bwd_f32(_ptr(x), _ptr(weight), _ptr(g), n, H, W, C, _ptr(dx), _ptr(dw), _ptr(db), _ptr(ws),
+                                         ws.numel() if ws is not None else 0, _stream(x.device))
+    _lib.check(rc, 'rmnet_pred_head_bwd_f32')
+    return dx, dw, db
+
+
+class _PredHeadFn(torch.autograd.Function):
+    """pred_head under autograd: saves x and the weight."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias):
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(x, weight)
+        return pred_head(x.detach(), weight.detach(), bias.detach())
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        if g is None:
+            return None, None, None
+        x, weight = ctx.saved_tensors
+        return pred_head_backward(x.detach(), weight.detach(), g.contiguous(), ctx.needs_input_grad[:3])
 
 
 def soft_aggregate_backward(dec, obj_begin, K, pad, prob, grad_prob=None, grad_logit=None, action=None):
@@ -1628,7 +1788,17 @@ def flow_stem(img0, img1, wpack, w_unscale, bias=None, pad=(0, 0, 0, 0), range_w
 def pred_head(x, weight, bias):
     """conv3x3_p1(relu(x), weight) + bias for a channels-last fp32 ``x`` [n, C, Hq, Wq] (C % 32 == 0) and ``weight`` [2, C, 3, 3],
     ``bias`` [2] -> NCHW-contiguous [n, 2, Hq, Wq], plain fp32 FMA (csrc/pred_head.hip): the decoder's prediction head with its
-    ReLU and the layout change inside.  No fall-back: anything else is a RuntimeError."""
+    ReLU and the layout change inside.  No fall-back: anything else is a RuntimeError.
+
+    Differentiable in ``x``, ``weight`` and ``bias``: when grad mode is on and ``x`` or ``weight`` requires grad, the call is recorded
+    as one ``torch.autograd.Function`` that saves x and the weight; the forward is the same launch, the backward is
+    ``pred_head_backward`` for what ``needs_input_grad`` asks for.  No double backward.  Every other call -- the inference path's,
+    which passes a detached copy of the weight next to the module's bias, among them -- takes the plain path and has no graph."""
+    if torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad for t in (x, weight)):
+        for t, name in ((x, 'x'), (weight, 'weight'), (bias, 'bias')):
+            if not isinstance(t, torch.Tensor):
+                raise RuntimeError('%s must be a torch.Tensor' % name)
+        return _PredHeadFn.apply(x, weight, bias)
     _check_act(x, 'x')
     if x.dim() != 4 or not x.is_contiguous(memory_format=torch.channels_last):
         raise RuntimeError('x must be a channels-last [n, C, Hq, Wq] tensor')
