@@ -388,6 +388,37 @@ int rmnet_conv3x3_wgrad_f32(const float *x, const float *g, const float *g_scale
 int rmnet_conv_grad_stage_f32(const float *g, const float *act, const float *amax, long long n, float *gs, float *g_scale,
                               void *stream);
 
+/* C1c gradients of the key / value heads (additive exports, same ABI version; csrc/conv_wgrad_n.hip).
+ *
+ * rmnet_conv3x3_wgrad_n_f32 is rmnet_conv3x3_wgrad_f32 for a gradient g [N, H, W, Cout] with Cout % 128 == 0: dw holds
+ * 9 * Cin * Cout elements as [co][ky][kx][ci], db [Cout] or NULL.  The same arithmetic element for element; the output channels are
+ * walked in tiles of 256 (the last one may hold 128) and the pixel ranges are planned for Cin / 16 * ceil(Cout / 256) workgroups
+ * each, so Cout == 256 returns the bits of rmnet_conv3x3_wgrad_f32 in dw, db and the range word.  Every rule of that entry holds
+ * with Cout in place of 256 (alignment, overlaps, RMNET_E_WORKSPACE against rmnet_conv3x3_wgrad_n_workspace_bytes, W <= 448,
+ * N*H*W*max(Cin, Cout) < 2^31 and 9*Cin*Cout < 2^31, the first call on a device outside capture); Cout <= 0 is
+ * RMNET_E_INVALID_ARG, Cout % 128 != 0 RMNET_E_UNSUPPORTED.  An element of g or pre(x) outside the window is counted once. */
+size_t rmnet_conv3x3_wgrad_n_workspace_bytes(int N, int H, int W, int Cin, int Cout);
+int rmnet_conv3x3_wgrad_n_f32(const float *x, const float *g, const float *g_scale, int flags, int N, int H, int W, int Cin, int Cout,
+                              float *dw, float *db, void *workspace, size_t workspace_bytes, int32_t *range_word, void *stream);
+
+/* The stage pass for a gradient that the memory read hands back: one launch, no host synchronisation.
+ *   gs[n, y, x, c] = g[n, c, y, x] * 2^s   where (x, y) lies inside image n's rectangle rects[n] = (cx0, cx1, cy0, cy1), inclusive
+ *                                          (clamped to the map, the convention of rmnet_conv_split_region_f32);
+ *                  = +0.0                  elsewhere: a select, whatever g holds there (NaN and Inf included) does not reach gs.
+ * rects NULL: every cell is inside.  s, *amax (taken before the mask) and g_scale are those of rmnet_conv_grad_stage_f32.
+ * gs is dense channels-last [N, H, W, C], C % 4 == 0.  layout says how g is laid out:
+ *   RMNET_GRAD_LAYOUT_NHWC    dense channels-last like gs (sn and sc are not looked at); gs may be g itself;
+ *   RMNET_GRAD_LAYOUT_PLANES  element (n, c, y, x) at g[n * sn + c * sc + y * W + x], sc >= H*W, sn >= (C - 1) * sc + H*W: an NCHW
+ *                             tensor, one tensor of the regional pair, a [:, :, t] slice of [N, C, T, H, W].
+ * gs and g_scale 16-byte aligned, g 16 (NHWC) or 4 (planes), amax and rects 4.  RMNET_E_INVALID_ARG for a NULL g / amax / gs /
+ * g_scale, a non-positive size, another layout, a misaligned pointer, planes that fold onto each other, or gs / g_scale
+ * overlapping an input (other than gs == g, NHWC) or each other; RMNET_E_UNSUPPORTED for C % 4 != 0 or 2^31 floats or more in gs
+ * or spanned by g. */
+#define RMNET_GRAD_LAYOUT_NHWC 0
+#define RMNET_GRAD_LAYOUT_PLANES 1
+int rmnet_conv_grad_stage_rect_f32(const float *g, int layout, long long sn, long long sc, const int32_t *rects, const float *amax,
+                                   int N, int C, int H, int W, float *gs, float *g_scale, void *stream);
+
 /* C1 trunk / key-value convolutions (additive export, same ABI version): the arithmetic, range word and flags of
  * rmnet_conv3x3_split_f32 for kernel size ksize = 1 or 3 (padding ksize / 2), stride 1 or 2 and Cout % 64 == 0 (csrc/conv_split.hip).
  * Replaces the ResNet-50 bottleneck convolutions (BatchNorm folded into the pack, skip add and ReLU in the epilogue) and the two

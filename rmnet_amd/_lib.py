@@ -105,6 +105,13 @@ SIGNATURES = {
         c_f32p, c_f32p, c_f32p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_f32p, c_f32p, ctypes.c_void_p,
         ctypes.c_size_t, c_i32p, ctypes.c_void_p]),
     'rmnet_conv_grad_stage_f32': (ctypes.c_int, [c_f32p, c_f32p, c_f32p, ctypes.c_longlong, c_f32p, c_f32p, ctypes.c_void_p]),
+    'rmnet_conv3x3_wgrad_n_workspace_bytes': (ctypes.c_size_t, [ctypes.c_int] * 5),
+    'rmnet_conv3x3_wgrad_n_f32': (ctypes.c_int, [
+        c_f32p, c_f32p, c_f32p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_f32p, c_f32p,
+        ctypes.c_void_p, ctypes.c_size_t, c_i32p, ctypes.c_void_p]),
+    'rmnet_conv_grad_stage_rect_f32': (ctypes.c_int, [
+        c_f32p, ctypes.c_int, ctypes.c_longlong, ctypes.c_longlong, c_i32p, c_f32p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+        ctypes.c_int, c_f32p, c_f32p, ctypes.c_void_p]),
     'rmnet_conv_split_f32': (ctypes.c_int, [
         c_f32p, ctypes.c_void_p, c_f32p, c_f32p, c_f32p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
         ctypes.c_int, ctypes.c_int, ctypes.c_int, c_f32p, c_f32p, ctypes.c_int, c_i32p, ctypes.c_void_p]),

@@ -11,7 +11,7 @@ CSRC = os.path.join(HERE, 'csrc')
 SOURCES = ['capi.hip', 'region_map.hip', 'flow_affine.hip', 'memory_read.hip', 'bank.hip', 'epilogue.hip', 'conv3x3.hip', 'conv3x3_rows.hip', 'conv_split.hip',
            'conv_rows.hip', 'stem.hip', 'pred_head.hip', 'flow_conv.hip', 'flow_head.hip', 'flow_stem.hip', 'boundary_f.hip', 'clip_io.hip', 'tta.hip',
            'late_objects.hip', 'val_loss.hip', 'memory_read_bwd.hip', 'val_loss_bwd.hip', 'soft_aggregate_bwd.hip', 'conv3x3_wgrad.hip',
-           'decoder_glue_bwd.hip']
+           'decoder_glue_bwd.hip', 'conv_wgrad_n.hip']
 LIB = os.path.join(HERE, 'librmnet_hip.so')
 ARCH = 'gfx950'
 

@@ -429,11 +429,12 @@ def conv_presplit():
     return PRESPLIT_DEFAULT if v is None else v.strip() != '0'
 
 
-def _split_path_ok(m, x, conv, backends):
+def _split_path_ok(m, x, conv, backends, any_mode=False):
     """Module ``m`` may run its convolutions on a split-fp16 kernel for input ``x``: fused epilogues on, packs present and allowed
-    (``m._conv_split``), eval, a CUDA fp32 4-D input with ``conv``'s channels in a channels-last run (the input or the network's
-    weights channels-last), and RMNET_CONV one of ``backends``.  Everything else keeps the MIOpen path."""
-    if not (getattr(m, '_fused', False) and getattr(m, '_conv_split', False)) or m.training:
+    (``m._conv_split``), eval (``any_mode``: or training -- for a module without BatchNorm), a CUDA fp32 4-D input with ``conv``'s
+    channels in a channels-last run (the input or the network's weights channels-last), and RMNET_CONV one of ``backends``.
+    Everything else keeps the MIOpen path."""
+    if not (getattr(m, '_fused', False) and getattr(m, '_conv_split', False)) or (m.training and not any_mode):
         return False
     if not (x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and x.shape[1] == conv.in_channels):
         return False
@@ -502,23 +503,69 @@ class KeyValue(nn.Module):
         self.key_conv = nn.Conv2d(indim, keydim, 3, padding=1)
         self.value_conv = nn.Conv2d(indim, valdim, 3, padding=1)
 
+    def device_grad_(self, enable=True):
+        """Opt in to (or out of) the heads' gradient on the device.  With the flag set, a call that autograd has to record -- grad
+        mode on and ``x`` or a head parameter requiring grad -- runs as ``ops._KeyValueFn`` in ``.train()`` and ``.eval()`` alike
+        (the module holds no BatchNorm): the forward is the launch of the fused path (dense or regional, the same bits), the
+        backward stages each head's gradient with its own scale (``ops.conv_grad_stage_rect``, masked by the rectangles on the
+        regional path), takes the weight / bias gradients from ``ops.conv3x3_wgrad`` and the data gradient from ``ops.kv_dgrad`` --
+        no atomics, the same bits from two ``backward()`` calls.  Provided the packs are there (``fuse_epilogues()``), the run is
+        channels-last CUDA fp32, RMNET_CONV allows the trunk kernels, both heads have a multiple of 128 outputs, Cin % 64 == 0
+        and the map is no wider than ``ops.WGRAD_MAX_W``.  The forward pack and the dgrad packs follow ``weight._version`` /
+        ``bias._version`` of both convolutions: rebuilt after an optimiser step, cached otherwise -- on this path only: before
+        inference with parameters that were updated in place, call ``fuse_epilogues()`` again, as ever.  Every other call takes the
+        path it took before.  Returns ``self``."""
+        self._device_grad = bool(enable)
+        return self
+
+    def _grad_path_ok(self, x):
+        if not getattr(self, '_device_grad', False) or not torch.is_grad_enabled():
+            return False
+        kc, vc = self.key_conv, self.value_conv
+        if not _split_path_ok(self, x, kc, ('full', 'split', 'trunk'), any_mode=True):
+            return False
+        from . import ops
+        if kc.out_channels % 128 or vc.out_channels % 128 or kc.in_channels % 64 or x.shape[3] > ops.WGRAD_MAX_W:
+            return False
+        return x.requires_grad or any(p.requires_grad for p in self.parameters())
+
+    def _grad_packs(self, need_x):
+        """(wpack, w_unscale, bias pair, dgrad packs) for the parameters as they are now (see ``device_grad_``)."""
+        from . import ops
+        kc, vc = self.key_conv, self.value_conv
+        params = (kc.weight, vc.weight, kc.bias, vc.bias)
+        now = tuple((p, p._version) for p in params)
+        same = lambda a, b: a is not None and len(a) == len(b) and all(p is q and v == u for (p, v), (q, u) in zip(a, b))
+        if not same(getattr(self, '_kv_ver', None), now):
+            with torch.no_grad():
+                wp, wu = ops.conv_split_pack(torch.cat((kc.weight, vc.weight)))
+                bkv = torch.cat((kc.bias, vc.bias)).contiguous()
+            self._buffers['_wp'], self._buffers['_wu'], self._buffers['_bkv'] = wp, wu, bkv
+            self._kv_ver = now
+        if not need_x:
+            return self._wp, self._wu, self._bkv, None
+        ent = self.__dict__.get('_kv_dgrad')
+        if ent is None or not same(ent[0], now[:2]):
+            ent = self.__dict__['_kv_dgrad'] = (now[:2], (ops.conv_split_dgrad_pack(kc.weight), ops.conv_split_dgrad_pack(vc.weight)))
+        return self._wp, self._wu, self._bkv, ent[1]
+
     def forward(self, x, rects=None):
         """(key, value), channels-last.  ``rects`` (int32 [N, 4] on the device, one cell rectangle per image): on the split-fp16 path
         with pre-split activations the heads are computed only inside the rectangles (``ops.conv_split(..., rects=)``) and come back
         NCHW-contiguous, +0.0 outside; on every other path, and for more images than the kernel's tables hold, ``rects`` is not
         looked at and the call is the one without it."""
-        if _split_path_ok(self, x, self.key_conv, ('full', 'split', 'trunk')):
-            # both heads in ONE launch of the split-fp16 kernel over the concatenated [key | value] pack, written as two tensors
+        if self._grad_path_ok(x):
             from . import ops
-            x = x.contiguous(memory_format=torch.channels_last)
-            rw = ops.conv_range_word(x.device)
-            if conv_presplit():
-                # r4 comes from another kernel: one pass splits it (and counts), instead of 9 taps x 5 Cout tiles doing so
-                x = ops.split_act(x, range_word=rw)
-                if rects is not None and x.shape[0] <= ops.KV_REGION_MAX_OBJECTS:
-                    return ops.conv_split(x, self._wp, self._wu, self._bkv, ksize=3, range_word=rw, split=self.key_conv.out_channels,
-                                          rects=rects)
-            return ops.conv_split(x, self._wp, self._wu, self._bkv, ksize=3, range_word=rw, split=self.key_conv.out_channels)
+            wp, wu, bkv, dp = self._grad_packs(x.requires_grad)
+            kc, vc = self.key_conv, self.value_conv
+            return ops._KeyValueFn.apply(x.contiguous(memory_format=torch.channels_last), kc.weight, kc.bias, vc.weight, vc.bias,
+                                         (wp, wu, bkv, kc.out_channels, dp, conv_presplit()), rects)
+        if _split_path_ok(self, x, self.key_conv, ('full', 'split', 'trunk')):
+            # both heads in ONE launch of the split-fp16 kernel over the concatenated [key | value] pack, written as two tensors;
+            # r4 comes from another kernel: one pass splits it (and counts), instead of 9 taps x 5 Cout tiles doing so
+            from . import ops
+            return ops.kv_heads(x.contiguous(memory_format=torch.channels_last), self._wp, self._wu, self._bkv,
+                                self.key_conv.out_channels, rects, conv_presplit())
         return self.key_conv(x), self.value_conv(x)
 
 
@@ -688,6 +735,8 @@ def fuse_epilogues_(module, enable=True):
             put(m, '_wp', wp)
             put(m, '_wu', wu)
             put(m, '_bkv', bkv)
+            # (KeyValue.device_grad_: the packs follow the parameters)
+            m._kv_ver = tuple((p, p._version) for p in (kc.weight, vc.weight, kc.bias, vc.bias)) if ok else None
             m._conv_split = ok and enable
         elif isinstance(m, (EncoderMemory, EncoderQuery)):
             sc, sh = _bn_scale_shift(m.bn1)

@@ -1013,14 +1013,15 @@ WGRAD_RANGE_MIN, WGRAD_MAX_RANGES, WGRAD_TARGET_WGS = 256, 64, 768
 WGRAD_BIAS_SPLIT = 8              # the bias gradient sums a range in that many chunks
 GRAD_TOP_EXP = 9                  # a staged gradient's largest element lies in [2^8, 2^9)
 
-# Launches made by the gradient path, counted on the Python side ('pack' counts conv3x3_dgrad_pack calls); tests reset and read it.
+# Launches made by the gradient path, counted on the Python side ('pack' counts conv3x3_dgrad_pack and conv_split_dgrad_pack calls); tests reset and read it.
 conv_grad_launches = {'stage': 0, 'wgrad': 0, 'dgrad': 0, 'pack': 0}
 
 
-def conv3x3_wgrad_plan(pixels, cin):
-    """(channel tiles, ranges, pixels per range) of ``conv3x3_wgrad`` for N*H*W = ``pixels``: csrc/conv3x3_wgrad.hip, wgrad_plan."""
+def conv3x3_wgrad_plan(pixels, cin, cout=256):
+    """(channel tiles, ranges, pixels per range) of ``conv3x3_wgrad`` for N*H*W = ``pixels`` and ``cout`` output channels, which are
+    walked in ceil(cout / 256) tiles that share the ranges: csrc/conv3x3_wgrad_parts.h, wgrad_plan."""
     nct = cin // WGRAD_CT
-    nr = max(1, min(WGRAD_TARGET_WGS // nct, -(-pixels // WGRAD_RANGE_MIN), WGRAD_MAX_RANGES))
+    nr = max(1, min(WGRAD_TARGET_WGS // (nct * -(-cout // CONV_COUT)), -(-pixels // WGRAD_RANGE_MIN), WGRAD_MAX_RANGES))
     rl = -(-(-(-pixels // nr)) // WGRAD_KT) * WGRAD_KT
     return nct, -(-pixels // rl), rl
 
@@ -1097,17 +1098,20 @@ def conv3x3_wgrad(x, g, g_scale, relu_in=False, want_bias=True, range_word=None)
     """The weight and bias gradient of ``conv3x3_split`` (csrc/conv3x3_wgrad.hip, include/rmnet_hip.h: rmnet_conv3x3_wgrad_f32):
     ``dW[co, ci, ky, kx] = sum g[n, co, y, x] * pre(x)[n, ci, y + ky - 1, x + kx - 1] / (g_scale[0] * g_scale[1])`` and
     ``db[co] = sum g[n, co, y, x] / (g_scale[0] * g_scale[1])`` for channels-last fp32 ``x`` [N, Cin, H, W] (the forward's input,
-    ``pre`` = ReLU under ``relu_in``) and ``g`` [N, 256, H, W] (the STAGED gradient of ``conv_grad_stage`` with its ``g_scale``;
-    ``torch.ones(2)`` for a gradient that is already inside |g| < 1023.5).  Returns ``(dW, db)``: dW a channels-last
-    [256, Cin, 3, 3] tensor, db [256] or None.  Deterministic: no atomics, the same bits on every call.  ``range_word``: the
-    backward's (``conv_grad_range_word``)."""
+    ``pre`` = ReLU under ``relu_in``) and ``g`` [N, Cout, H, W], Cout % 128 == 0 (the STAGED gradient of ``conv_grad_stage`` or
+    ``conv_grad_stage_rect`` with its ``g_scale``; ``torch.ones(2)`` for a gradient that is already inside |g| < 1023.5).  Returns
+    ``(dW, db)``: dW a channels-last [Cout, Cin, 3, 3] tensor, db [Cout] or None.  Deterministic: no atomics, the same bits on
+    every call.  Cout = 256 runs rmnet_conv3x3_wgrad_f32, every other width rmnet_conv3x3_wgrad_n_f32 (csrc/conv_wgrad_n.hip: the
+    same arithmetic over tiles of output channels).  ``range_word``: the backward's (``conv_grad_range_word``)."""
     for t, n in ((x, 'x'), (g, 'g')):
         _check_act(t, n)
         if t.dim() != 4 or not t.is_contiguous(memory_format=torch.channels_last):
             raise RuntimeError('%s must be a channels-last 4-D tensor' % n)
     N, cin, H, W = x.shape
-    if tuple(g.shape) != (N, CONV_COUT, H, W):
-        raise RuntimeError('g must be [N, 256, H, W] for x [N, Cin, H, W], got %s and %s' % (tuple(g.shape), tuple(x.shape)))
+    cout = g.shape[1]
+    if tuple(g.shape) != (N, cout, H, W) or cout % 128 or cout == 0:
+        raise RuntimeError('g must be [N, Cout, H, W] with Cout %% 128 == 0 for x [N, Cin, H, W], got %s and %s'
+                           % (tuple(g.shape), tuple(x.shape)))
     if cin % 32:
         raise RuntimeError('conv3x3_wgrad needs Cin % 32 == 0, got %d' % cin)
     _check(g_scale, 'g_scale')
@@ -1118,15 +1122,23 @@ def conv3x3_wgrad(x, g, g_scale, relu_in=False, want_bias=True, range_word=None)
     for t in (g, g_scale, range_word):
         if t is not None and t.device != x.device:
             raise RuntimeError('conv3x3_wgrad: every tensor must be on %s' % x.device)
-    dw = torch.empty((CONV_COUT, cin, 3, 3), dtype=torch.float32, device=x.device, memory_format=torch.channels_last)
-    db = torch.empty(CONV_COUT, dtype=torch.float32, device=x.device) if want_bias else None
+    dw = torch.empty((cout, cin, 3, 3), dtype=torch.float32, device=x.device, memory_format=torch.channels_last)
+    db = torch.empty(cout, dtype=torch.float32, device=x.device) if want_bias else None
     lib = _lib.load()
-    nbytes = lib.rmnet_conv3x3_wgrad_workspace_bytes(N, H, W, cin)
-    ws = _ws(nbytes, x.device)
-    with torch.cuda.device(x.device):
-        rc = lib.rmnet_conv3x3_wgrad_f32(_ptr(x), _ptr(g), _ptr(g_scale), CONV_RELU_IN if relu_in else 0, N, H, W, cin, _ptr(dw),
-                                         _ptr(db), _ptr(ws), ws.numel(), _ptr(range_word), _stream(x.device))
-    _lib.check(rc, 'rmnet_conv3x3_wgrad_f32')
+    flags = CONV_RELU_IN if relu_in else 0
+    if cout == CONV_COUT:
+        what = 'rmnet_conv3x3_wgrad_f32'
+        ws = _ws(lib.rmnet_conv3x3_wgrad_workspace_bytes(N, H, W, cin), x.device)
+        with torch.cuda.device(x.device):
+            rc = lib.rmnet_conv3x3_wgrad_f32(_ptr(x), _ptr(g), _ptr(g_scale), flags, N, H, W, cin, _ptr(dw), _ptr(db), _ptr(ws),
+                                             ws.numel(), _ptr(range_word), _stream(x.device))
+    else:
+        what = 'rmnet_conv3x3_wgrad_n_f32'
+        ws = _ws(lib.rmnet_conv3x3_wgrad_n_workspace_bytes(N, H, W, cin, cout), x.device)
+        with torch.cuda.device(x.device):
+            rc = lib.rmnet_conv3x3_wgrad_n_f32(_ptr(x), _ptr(g), _ptr(g_scale), flags, N, H, W, cin, cout, _ptr(dw), _ptr(db), _ptr(ws),
+                                               ws.numel(), _ptr(range_word), _stream(x.device))
+    _lib.check(rc, what)
     conv_grad_launches['wgrad'] += 1
     return dw, db
 
@@ -1187,6 +1199,158 @@ class _Conv3x3SplitFn(torch.autograd.Function):
             gm = g if out is None else (gr if gr is not None else torch.ops.aten.threshold_backward(g, out, 0))
             gb = gm.sum(dim=(0, 2, 3))
         return gx, gw, gb, gr, None, None, None, None, None, None
+
+
+# ---- gradients of the key / value heads (csrc/conv_wgrad_n.hip; the data gradient is conv_split on flipped packs) -----------------
+GRAD_LAYOUT_NHWC, GRAD_LAYOUT_PLANES = 0, 1   # RMNET_GRAD_LAYOUT_*
+
+
+def _planes_strides(g):
+    """(sn, sc) when 4-D ``g`` is made of H x W planes that are dense in themselves and do not fold onto each other, else None."""
+    N, C, H, W = g.shape
+    st = g.stride()
+    if (W > 1 and st[3] != 1) or (H > 1 and st[2] != W):
+        return None
+    sc = st[1] if C > 1 else H * W
+    sn = st[0] if N > 1 else (C - 1) * sc + H * W
+    return (sn, sc) if sc >= H * W and sn >= (C - 1) * sc + H * W else None
+
+
+def conv_grad_stage_rect(g, rects=None, amax=None):
+    """The stage pass for the gradients the memory read hands back (csrc/conv_wgrad_n.hip: grad_stage_rect), one kernel and no host
+    synchronisation: ``gs`` = a new dense channels-last [N, C, H, W] tensor with ``gs[n, c, y, x] = g[n, c, y, x] * 2^s`` where
+    (x, y) lies inside ``rects[n]`` = (cx0, cx1, cy0, cy1) (int32 [N, 4] on the device, inclusive, clamped to the map: the
+    convention of ``conv_split(..., rects=)``) and +0.0 elsewhere -- a select: NaN or Inf outside a rectangle does not reach
+    ``gs``.  Without ``rects`` it is a layout + scale pass.  ``g`` (fp32, C % 4 == 0) is channels-last dense, or made of planes:
+    element (n, c, y, x) at ``n * sn + c * sc + y * W + x`` (an NCHW tensor, one of the regional pair, a ``[:, :, t]`` slice of
+    [no, C, Tcap, h, w]).  ``s = conv_grad_stage_exponent(amax)``; ``amax`` is a 0-dim upper bound of |g| on the device, taken
+    before the mask (default: the largest |element| of ``g`` as given, one reduction).  Returns ``(gs, g_scale)`` as
+    ``conv_grad_stage`` does."""
+    if not isinstance(g, torch.Tensor) or not g.is_cuda or g.dtype != torch.float32:
+        raise RuntimeError('g must be a CUDA torch.float32 tensor')
+    if g.dim() != 4 or g.numel() == 0 or g.shape[1] % 4:
+        raise RuntimeError('conv_grad_stage_rect needs a non-empty [N, C, H, W] g with C %% 4 == 0, got %s' % (tuple(g.shape),))
+    N, C, H, W = g.shape
+    if g.is_contiguous(memory_format=torch.channels_last):
+        layout, sn, sc = GRAD_LAYOUT_NHWC, 0, 0
+    else:
+        st = _planes_strides(g)
+        if st is None:
+            raise RuntimeError('conv_grad_stage_rect: g must be channels-last dense or made of dense H x W planes, got strides %s'
+                               % (g.stride(),))
+        layout, (sn, sc) = GRAD_LAYOUT_PLANES, st
+    if amax is None:
+        amax = torch.linalg.vector_norm(g, float('inf'))
+    _check(amax, 'amax')
+    if amax.numel() != 1:
+        raise RuntimeError('amax must hold one element')
+    if rects is not None:
+        _check(rects, 'rects', torch.int32)
+        if tuple(rects.shape) != (N, 4) or not rects.is_contiguous():
+            raise RuntimeError('rects must be a contiguous [N, 4] = %s tensor, got %s' % ((N, 4), tuple(rects.shape)))
+    for t in (amax, rects):
+        if t is not None and t.device != g.device:
+            raise RuntimeError('conv_grad_stage_rect: every tensor must be on %s' % g.device)
+    gs = torch.empty((N, C, H, W), dtype=torch.float32, device=g.device, memory_format=torch.channels_last)
+    g_scale = torch.empty(4, dtype=torch.float32, device=g.device)[:2]
+    with torch.cuda.device(g.device):
+        rc = _lib.load().rmnet_conv_grad_stage_rect_f32(_ptr(g), layout, sn, sc, _ptr(rects), _ptr(amax), N, C, H, W, _ptr(gs),
+                                                        _ptr(g_scale), _stream(g.device))
+    _lib.check(rc, 'rmnet_conv_grad_stage_rect_f32')
+    conv_grad_launches['stage'] += 1
+    return gs, g_scale
+
+
+@torch.no_grad()
+def conv_split_dgrad_pack(weight):
+    """The pack of the data gradient of a [Cout, Cin, 3, 3] stride 1 / pad 1 convolution on ``conv_split``, Cout % 32 == 0 and
+    Cin % 64 == 0: dX = conv(G, W transposed and flipped), a convolution with Cout inputs and Cin outputs.  Returns
+    ``conv_split_pack(weight.transpose(0, 1).flip(2, 3))``."""
+    if weight.dim() != 4 or tuple(weight.shape[2:]) != (3, 3) or weight.shape[0] % 32 or weight.shape[1] % 64:
+        raise RuntimeError('conv_split_dgrad_pack needs a [Cout, Cin, 3, 3] weight with Cout %% 32 == 0 and Cin %% 64 == 0, got %s'
+                           % (tuple(weight.shape),))
+    conv_grad_launches['pack'] += 1
+    return conv_split_pack(weight.detach().transpose(0, 1).flip(2, 3))
+
+
+def kv_dgrad(gs_key, scale_key, gs_val, scale_val, packs, range_word=None):
+    """The data gradient of the two key / value heads from their staged gradients (``conv_grad_stage_rect``; fp32 channels-last
+    [N, keydim, H, W] and [N, valdim, H, W], each with its OWN staging scale): ``packs`` = the two ``conv_split_dgrad_pack``
+    results, key head first.  Two ``conv_split`` calls (ksize 3, stride 1): the first writes dX of the key head, the second takes
+    it as ``res`` and ``out``; each uses ``w_unscale / (g_scale[0] * g_scale[1])`` of its own head (exact: powers of two).  A head
+    given as None launches nothing.  ``range_word``: the backward's (``conv_grad_range_word``)."""
+    dx = None
+    for gs, sc, (wp, wu) in ((gs_key, scale_key, packs[0]), (gs_val, scale_val, packs[1])):
+        if gs is None:
+            continue
+        inv = sc.reciprocal()
+        dx = conv_split(gs, wp, wu * inv[0] * inv[1], res=dx, ksize=3, out=dx, range_word=range_word)
+        conv_grad_launches['dgrad'] += 1
+    if dx is None:
+        raise RuntimeError('kv_dgrad: at least one head must have a gradient')
+    return dx
+
+
+def kv_heads(x, wpack, w_unscale, bias, split, rects=None, presplit=True):
+    """The two key / value heads in one launch over their concatenated pack: (key, value) for a channels-last fp32 ``x``.  With
+    ``presplit`` x is split once (``split_act``); with ``rects`` as well (and no more images than KV_REGION_MAX_OBJECTS) the
+    heads are computed only inside the rectangles and come back NCHW-contiguous (``conv_split(..., rects=)``)."""
+    rw = conv_range_word(x.device)
+    if presplit:
+        x = split_act(x, range_word=rw)
+        if kv_regional(x.shape[0], rects, presplit):
+            return conv_split(x, wpack, w_unscale, bias, ksize=3, range_word=rw, split=split, rects=rects)
+    return conv_split(x, wpack, w_unscale, bias, ksize=3, range_word=rw, split=split)
+
+
+def kv_regional(n, rects, presplit):
+    """Whether ``kv_heads`` runs the regional kernel for ``n`` images."""
+    return bool(presplit) and rects is not None and n <= KV_REGION_MAX_OBJECTS
+
+
+class _KeyValueFn(torch.autograd.Function):
+    """The key / value heads under autograd (``KeyValue.device_grad_``): the forward is ``kv_heads``; saves x and the rectangles,
+    nothing else.  ``pack`` = (wpack, w_unscale, bias of both heads, split, dgrad packs or None, presplit)."""
+
+    @staticmethod
+    def forward(ctx, x, w_key, b_key, w_val, b_val, pack, rects):
+        wp, wu, bkv, split, dgrad_packs, presplit = pack
+        if ctx.needs_input_grad[0] and dgrad_packs is None:
+            raise RuntimeError('_KeyValueFn: the gradient with respect to x needs the dgrad packs')
+        key, value = kv_heads(x.detach(), wp, wu, bkv, split, rects, presplit)
+        ctx.regional = kv_regional(x.shape[0], rects, presplit)
+        ctx.dgrad_packs = dgrad_packs if ctx.needs_input_grad[0] else None
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(x, *((rects,) if ctx.regional else ()))
+        return key, value
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_key, g_val):
+        saved = ctx.saved_tensors
+        x = saved[0].detach()
+        rects = saved[1] if ctx.regional else None
+        need_x = ctx.needs_input_grad[0]
+        grw = conv_grad_range_word(x.device)
+        staged, grads = [], []
+        for g, need_w, need_b in ((g_key, ctx.needs_input_grad[1], ctx.needs_input_grad[2]),
+                                  (g_val, ctx.needs_input_grad[3], ctx.needs_input_grad[4])):
+            gs = sc = gw = gb = None
+            if g is not None and (need_x or need_w or need_b):
+                if not g.is_contiguous(memory_format=torch.channels_last) and _planes_strides(g) is None:
+                    g = g.contiguous()                                      # (an expanded grad_output becomes a plain tensor)
+                gs, sc = conv_grad_stage_rect(g, rects)
+                if need_w:
+                    gw, gb = conv3x3_wgrad(x, gs, sc, want_bias=need_b, range_word=grw)
+                elif need_b:                                                # (a trainable bias on frozen weights: no GEMM)
+                    inv = sc.reciprocal()
+                    gb = gs.sum(dim=(0, 2, 3)) * inv[0] * inv[1]
+            staged += [gs, sc]
+            grads += [gw, gb]
+        gx = None
+        if need_x and (staged[0] is not None or staged[2] is not None):
+            gx = kv_dgrad(staged[0], staged[1], staged[2], staged[3], ctx.dgrad_packs, range_word=grw)
+        return (gx,) + tuple(grads) + (None, None)
 
 
 @torch.no_grad()
